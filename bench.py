@@ -1,7 +1,7 @@
 """Throughput of the MI355X Sep-TFAnet^VAD forward path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f16x3|fp32|bf16|f16]
-                    [--workload offline|cfg4|cfg5|long|stream]
+                    [--workload offline|cfg4|cfg5|long|stream] [--dump-outputs DIR] [--full]
 
 One step = one ``SeparationModel.forward`` (config_with_vad.json) over a resident batch of 64
 synthetic 2-speaker mixtures of 32 000 samples (4 s @ 8 kHz resampled to 16 kHz by the
@@ -11,7 +11,11 @@ starts them itself (a child torch.distributed.run, before this process touches t
 runs its own shard of utterances (weak scaling, no collective on the data path, only barriers around
 the timed region and a max-reduce of the elapsed time). Rank 0 prints one JSON line.
 
-Extra fields:
+A run without --full sets up, warms up, times the K steps, writes the outputs of the last timed step if
+--dump-outputs is given (DIR/sep.npy, vad.npy, est.npy; cfg 3: online_signal.npy; same arguments, same inputs)
+and prints the line. --full adds the legs that take runs of their own:
+
+Extra fields with --full:
   roofline      (+ weight_stream: the per-CU weight bytes of the launch, their rate, and the texture-path
                 busy fraction from the committed counters — the decomposition's real floor)
                 dominant kernel = k_tcn, the fused persistent TCN (24 blocks of conv1d 256->256, depthwise
@@ -295,9 +299,36 @@ def _reduce_dev(dist, dev):
     return "cpu" if dist is not None and dist.get_backend() == "gloo" else dev
 
 
-def timed_region(step, steps, warmup, dist=None, sync=lambda: None, reduce_device="cpu"):
+DUMP_BUDGET = 64 * 10 ** 6  # bytes, all arrays of one --dump-outputs together
+
+
+def dump_outputs(dirname, arrays, rank=0):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as DIR/<name>.npy (ranks above 0: <name>.rank<r>.npy),
+    float64 kept, everything else float32, complex values as [..., 2] (re, im) pairs. Above DUMP_BUDGET bytes in all,
+    each array keeps its share of the budget as a fixed sample of its flattened elements (PCG64 seed 0, ascending
+    indices), the same elements for the same shapes."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        if not torch.is_tensor(t):
+            continue  # a configuration without VAD returns 0 in its place
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        host[name] = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BUDGET:
+            keep = int(DUMP_BUDGET * (a.nbytes / total)) // a.itemsize
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
+def timed_region(step, steps, warmup, dist=None, sync=lambda: None, reduce_device="cpu", keep=None):
     """W untimed warmup steps, then EXACTLY `steps` steps bracketed by a barrier + device sync on both
-    sides; returns the elapsed seconds, max over ranks (the driver contract)."""
+    sides; returns the elapsed seconds, max over ranks (the driver contract). `keep` (a list) receives what
+    the last timed step returned."""
     for _ in range(warmup):
         step()
     sync()
@@ -309,14 +340,17 @@ def timed_region(step, steps, warmup, dist=None, sync=lambda: None, reduce_devic
 
     barrier()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step()
+    last = step() if steps > 0 else None
     barrier()
     el = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([el], device=reduce_device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if keep is not None:
+        keep.append(last)
     return el
 
 
@@ -355,6 +389,8 @@ def bench_stream(args):
     el = timed_region(step, args.steps, args.warmup, dist, torch.cuda.synchronize, _reduce_dev(dist, dev))
     if os.environ.get("SEPVAD_BENCH_DUMP"):  # tests: this rank's stitched streams after the last step
         np.save(f"{os.environ['SEPVAD_BENCH_DUMP']}.rank{rank}.npy", ons.online_signal.cpu().numpy())
+    if args.dump_outputs:  # this rank's stitched streams after the last step (what calc_online leaves its caller)
+        dump_outputs(args.dump_outputs, {"online_signal": ons.online_signal}, rank)
     if rank == 0:
         windows = world * n_streams * n_win * args.steps
         out = {
@@ -375,6 +411,17 @@ def bench_stream(args):
         dist.destroy_process_group()
 
 
+def make_inputs(workload, B, N, rank=0):
+    """This rank's shard of utterances, global utterance ids [rank*B, (rank+1)*B): float32 [B][N], seeded per
+    utterance id, so the same arguments give the same array in every run."""
+    from sep_tfanet_vad_amd import synth
+    if workload == "cfg4":  # image-method reverberant mixtures (RT60 U[0.2, 0.6] s; host RIR generator)
+        x, _ = synth.make_reverb_batch(B, N, 40_000 + rank * B)
+    else:
+        x, _ = synth.make_batch(B, N, 10_000 + rank * B)
+    return x
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -386,6 +433,13 @@ def main():
     ap.add_argument("--samples", type=int, default=None)
     ap.add_argument("--split", type=int, default=DEFAULT_SPLIT,
                     help="concurrent utterance chunks per forward (internal streams; bitwise-identical results)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs of their own: the per-kernel timing pass behind `roofline` and "
+                         "the CPU baseline (`cpu_baseline`, offline workload on one GPU; --no-cpu-baseline leaves it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (sep, vad, "
+                         "est; stream: online_signal) in float32, complex values as (re, im) pairs; at most 64 MB in "
+                         "all, a fixed seeded sample of larger outputs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "fp32", "bf16", "f16"],
@@ -433,12 +487,7 @@ def main():
     B = args.batch or B0
     N = args.samples or N0
     T = 1 + N // 256
-    # this rank's shard of utterances: global utterance ids [rank*B, (rank+1)*B)
-    if args.workload == "cfg4":  # image-method reverberant mixtures (RT60 U[0.2, 0.6] s; host RIR generator)
-        x, _ = synth.make_reverb_batch(B, N, 40_000 + rank * B)
-    else:
-        x, _ = synth.make_batch(B, N, 10_000 + rank * B)
-    x = torch.from_numpy(x).to(dev)
+    x = torch.from_numpy(make_inputs(args.workload, B, N, rank)).to(dev)
     h = net.native_handle(dev)
     h.reserve(B, N)
     h.set_split(args.split)
@@ -448,18 +497,23 @@ def main():
             return net(x)
 
     # timed region (value)
-    el = timed_region(step, args.steps, args.warmup, dist, torch.cuda.synchronize, _reduce_dev(dist, dev))
+    last = []
+    el = timed_region(step, args.steps, args.warmup, dist, torch.cuda.synchronize, _reduce_dev(dist, dev), keep=last)
+    if args.dump_outputs:  # forward's return of the last timed step, before anything else runs
+        dump_outputs(args.dump_outputs, dict(zip(("sep", "vad", "est"), last[0])), rank)
+    del last
 
-    # per-kernel timing pass (HIP events on the kernels' stream), same steps
-    h.set_timing(True)
-    gemm_ms = res_ms = tot_ms = 0.0
-    n_res = n_gemm = 0
-    for _ in range(max(3, min(args.steps, 10))):
-        step()
-        tm = h.timing()
-        gemm_ms += tm["gemm_ms"]; res_ms += tm["res_out_ms"]; tot_ms += tm["total_ms"]
-        n_res += tm["res_out_launches"]; n_gemm += tm["gemm_launches"]
-    h.set_timing(False)
+    if args.full:
+        # per-kernel timing pass (HIP events on the kernels' stream), same steps
+        h.set_timing(True)
+        gemm_ms = res_ms = tot_ms = 0.0
+        n_res = n_gemm = 0
+        for _ in range(max(3, min(args.steps, 10))):
+            step()
+            tm = h.timing()
+            gemm_ms += tm["gemm_ms"]; res_ms += tm["res_out_ms"]; tot_ms += tm["total_ms"]
+            n_res += tm["res_out_launches"]; n_gemm += tm["gemm_launches"]
+        h.set_timing(False)
     fused = h.fused_status()  # synchronises; raises if a fused hand-off gave up
     # two-slice launches stream the int8 lo plane's values as fp16 (api.hip twfq, SEPVAD_TCN_WQ16): 4 bytes per weight
     wlo_streamed, nsl = args.wlo, (h.fused_slices() if fused else 1)
@@ -467,9 +521,8 @@ def main():
             and os.environ.get("SEPVAD_TCN_WQ16", "1") != "0":
         wlo_streamed = "f16"
 
-    if rank == 0:
-        total_utt = world * B * args.steps
-        value = total_utt / el
+    roofline = None
+    if rank == 0 and args.full:
         res_avg_s = res_ms / n_res / 1e3
         if fused:
             # dominant kernel = the fused persistent TCN (all 24 blocks in one launch)
@@ -511,6 +564,36 @@ def main():
                 traffic_src = "profiles/" + pmc_name
             except (OSError, ValueError, KeyError):
                 traffic = None
+        roofline = {
+            "bound": "mfma",
+            "kernel": kern,
+            "achieved": round(achieved, 3),
+            "peak": round(peak, 1),
+            "unit": "TFLOP/s",
+            "frac": round(achieved / peak, 4),
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": bytes_launch,
+            "flops_per_launch": flops_launch,
+            "avg_launch_us": round(res_avg_s * 1e6, 2),
+            "all_gemms_tflops": round(all_gemm_tflops, 3) if all_gemm_tflops else None,
+            "gemm_share_of_forward": round(gemm_ms / tot_ms, 3) if tot_ms > 0 else None,
+        }
+        if fused:
+            roofline["weight_stream"] = weight_stream(B, T, args.precision, res_avg_s, wlo=wlo_streamed, nsl=nsl)
+            if args.precision == "f16x3" and args.wlo == PMC_WLO and B == B_PER_GPU and N == N_SAMPLES:
+                roofline["caches"] = cache_counters(args.wlo)
+            # the same fraction from the committed rocprofv3 average of the kernel (headline configuration only)
+            if args.precision == "f16x3" and args.wlo == PMC_WLO and B == B_PER_GPU and N == N_SAMPLES:
+                rp = rocprof_avg_us(TCN_KERNEL_PREFIX)
+                if rp:
+                    roofline["rocprof"] = {"avg_launch_us": round(rp, 2),
+                                           "achieved": round(flops_launch / (rp * 1e-6) / 1e12, 3),
+                                           "frac": round(flops_launch / (rp * 1e-6) / 1e12 / peak, 4),
+                                           "source": "profiles/" + STATS_FILE}
+    if rank == 0:
+        total_utt = world * B * args.steps
+        value = total_utt / el
         out = {
             "metric": METRIC,
             "value": round(value, 2),
@@ -548,35 +631,10 @@ def main():
                 "seq_len": N,
                 "parallelism": f"dp{world} (independent utterance shards, no data-path collective)",
             },
-            "roofline": {
-                "bound": "mfma",
-                "kernel": kern,
-                "achieved": round(achieved, 3),
-                "peak": round(peak, 1),
-                "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4),
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": bytes_launch,
-                "flops_per_launch": flops_launch,
-                "avg_launch_us": round(res_avg_s * 1e6, 2),
-                "all_gemms_tflops": round(all_gemm_tflops, 3) if all_gemm_tflops else None,
-                "gemm_share_of_forward": round(gemm_ms / tot_ms, 3) if tot_ms > 0 else None,
-            },
         }
-        if fused:
-            out["roofline"]["weight_stream"] = weight_stream(B, T, args.precision, res_avg_s, wlo=wlo_streamed, nsl=nsl)
-            if args.precision == "f16x3" and args.wlo == PMC_WLO and B == B_PER_GPU and N == N_SAMPLES:
-                out["roofline"]["caches"] = cache_counters(args.wlo)
-            # the same fraction from the committed rocprofv3 average of the kernel (headline configuration only)
-            if args.precision == "f16x3" and args.wlo == PMC_WLO and B == B_PER_GPU and N == N_SAMPLES:
-                rp = rocprof_avg_us(TCN_KERNEL_PREFIX)
-                if rp:
-                    out["roofline"]["rocprof"] = {"avg_launch_us": round(rp, 2),
-                                                  "achieved": round(flops_launch / (rp * 1e-6) / 1e12, 3),
-                                                  "frac": round(flops_launch / (rp * 1e-6) / 1e12 / peak, 4),
-                                                  "source": "profiles/" + STATS_FILE}
-        if world == 1 and not args.no_cpu_baseline and args.workload == "offline":
+        if roofline is not None:
+            out["roofline"] = roofline
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "offline":
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         emit(out)
     if dist is not None:

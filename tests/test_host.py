@@ -147,3 +147,26 @@ def test_unknown_weight_lo_is_rejected(monkeypatch):
         pkg.SeparationModel(**pkg.CONFIG_WITH_VAD)
     monkeypatch.setenv("SEPVAD_WLO", "e4m3")
     assert pkg.SeparationModel(**pkg.CONFIG_WITH_VAD).native_weight_lo == "e4m3"
+
+
+def test_dump_outputs_samples_above_its_budget(tmp_path):
+    """dump_outputs on host tensors: float64 kept, complex as (re, im) pairs, and above the budget a fixed sample whose
+    size keeps all files together within it: the same elements for the same shapes."""
+    import numpy as np
+    import bench
+    a = torch.arange(5 * 10 ** 6, dtype=torch.float32).reshape(5, -1)          # 20 MB
+    c = torch.complex(torch.arange(7 * 10 ** 6, dtype=torch.float32), torch.ones(7 * 10 ** 6))  # 56 MB
+    e = torch.arange(10, dtype=torch.float64)
+    for sub in ("r1", "r2"):
+        bench.dump_outputs(str(tmp_path / sub), {"a": a, "c": c, "e": e, "none": 0})
+    out = {n: np.load(str(tmp_path / "r1" / f"{n}.npy")) for n in ("a", "c", "e")}
+    assert sorted(f.name for f in (tmp_path / "r1").iterdir()) == ["a.npy", "c.npy", "e.npy"]
+    assert out["a"].dtype == np.float32 and out["c"].dtype == np.float32 and out["e"].dtype == np.float64
+    total = sum(v.nbytes for v in out.values())
+    assert 0.99 * bench.DUMP_BUDGET <= total <= bench.DUMP_BUDGET
+    assert out["a"].ndim == 1 and np.all(np.diff(out["a"]) > 0) and 0 < out["a"].size < a.numel()
+    for n in out:
+        assert np.array_equal(out[n], np.load(str(tmp_path / "r2" / f"{n}.npy")))
+    bench.dump_outputs(str(tmp_path / "small"), {"c": c[:3], "e": e})
+    assert np.array_equal(np.load(str(tmp_path / "small" / "c.npy")), [[0, 1], [1, 1], [2, 1]])
+    assert np.array_equal(np.load(str(tmp_path / "small" / "e.npy")), e.numpy())

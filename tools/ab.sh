@@ -9,7 +9,7 @@ for r in $(seq 1 $rounds); do
   for spec in "$@"; do
     lib=${spec%%@*}; envs=""; n=$(basename $lib .so)
     if [ "$spec" != "$lib" ]; then envs=${spec#*@}; n=$n.${envs##*=}; fi
-    env $envs SEPVAD_LIB=$PWD/$lib timeout -k 10 120 python3 bench.py --no-cpu-baseline $AB_ARGS > $out/$n.$r.json 2> $out/$n.$r.err || exit 1
+    env $envs SEPVAD_LIB=$PWD/$lib timeout -k 10 120 python3 bench.py --full --no-cpu-baseline $AB_ARGS > $out/$n.$r.json 2> $out/$n.$r.err || exit 1
     python3 -c "import json; d=json.loads(open('$out/$n.$r.json').read().strip().splitlines()[-1]); print('$n', $r, d['value'], d['roofline']['avg_launch_us'], d['ms_per_step'])"
   done
 done | tee $out/ab.txt

@@ -5,7 +5,7 @@ tag=$1; rounds=$2; shift 2
 out=gpurun_out/$tag; mkdir -p $out
 for r in $(seq 1 $rounds); do
   for e in "$@"; do
-    env $e timeout -k 10 120 python3 bench.py --no-cpu-baseline $AB_ARGS > $out/${e//=/_}.$r.json 2> $out/${e//=/_}.$r.err || exit 1
+    env $e timeout -k 10 120 python3 bench.py --full --no-cpu-baseline $AB_ARGS > $out/${e//=/_}.$r.json 2> $out/${e//=/_}.$r.err || exit 1
     python3 -c "import json; d=json.loads(open('$out/${e//=/_}.$r.json').read().strip().splitlines()[-1]); print('${e//=/_}', $r, d['value'], d['roofline']['avg_launch_us'], d['ms_per_step'])"
   done
 done | tee $out/ab.txt

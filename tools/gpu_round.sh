@@ -14,7 +14,7 @@ step smoke && timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(
 && tail -2 $out/smoke.log \
 && { [ -n "$skip" ] || { step pytest && timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 \
        --timeout-method thread > $out/pytest.log 2>&1; rc=$?; tail -4 $out/pytest.log; [ $rc -eq 0 ]; }; } \
-&& step bench && timeout -k 10 400 python3 bench.py > $out/bench.json 2> $out/bench.err \
+&& step bench && timeout -k 10 400 python3 bench.py --full > $out/bench.json 2> $out/bench.err \
 && cat $out/bench.json \
 && step rocprof && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run \
        -- $bench > $out/prof.log 2>&1 \

@@ -10,6 +10,6 @@ tail -1 $out/pytest.log
 bash tools/probe_round.sh $tag $arms > $out/probe.log 2>&1 || { tail -20 $out/probe.log; exit 1; }
 grep -E "^==|per block|conv1d|epilogue|P1|dwconv|res_out|P2|rowsum|P3|gates|moments|P4|x' update" $out/probe.log | grep -v "per-wave\|    " 
 for p in $arms; do
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --precision $p > $out/bench_$p.json 2> $out/bench_$p.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --precision $p > $out/bench_$p.json 2> $out/bench_$p.err || exit 1
   python3 -c "import json; d=json.loads(open('$out/bench_$p.json').read().strip().splitlines()[-1]); print('$p', d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'], d['roofline']['frac'])"
 done

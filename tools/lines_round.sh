@@ -3,7 +3,7 @@
 # weight lo planes. usage: bash tools/lines_round.sh <tag>
 set -o pipefail
 out=gpurun_out/${1:-lines}; mkdir -p $out
-run() { n=$1; shift; echo "== $n $(date +%T)"; timeout -k 10 300 python3 bench.py "$@" > $out/$n.json 2> $out/$n.err && tail -1 $out/$n.json | cut -c1-160; }
+run() { n=$1; shift; echo "== $n $(date +%T)"; timeout -k 10 300 python3 bench.py --full "$@" > $out/$n.json 2> $out/$n.err && tail -1 $out/$n.json | cut -c1-160; }
 run offline_f16x3 \
 && run offline_bf16 --no-cpu-baseline --precision bf16 \
 && run cfg4_f16x3 --no-cpu-baseline --workload cfg4 \

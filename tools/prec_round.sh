@@ -9,6 +9,6 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
     || { tail -30 $out/pytest.log; exit 1; }
 tail -2 $out/pytest.log
 for p in f16x3 bf16 f16; do
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --precision $p > $out/bench_$p.json 2> $out/bench_$p.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --precision $p > $out/bench_$p.json 2> $out/bench_$p.err || exit 1
   python3 -c "import json; d=json.loads(open('$out/bench_$p.json').read().strip().splitlines()[-1]); print('$p', d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'], d['roofline']['frac'])"
 done
