@@ -406,20 +406,23 @@ def test_vad_taps_finished_in_istft(nets):
     assert np.abs(vg.cpu().numpy() - g["vad"]).max() <= VAD_PROB_TOL
 
 
-def test_vad_taps_in_istft_default_short_utterances(nets):
+@pytest.mark.parametrize("B,N", [(9, 32000), (1, 32000), (3, 31900), (2, 2560)])
+def test_vad_taps_in_istft_default_short_utterances(B, N, nets, monkeypatch):
     """T <= 256 defaults to the in-k_istft_pair VAD features (SEPVAD_VAD_FEAT unset); they take k_vad_feat<4>'s items
     and summation order; the BN_1 affine rounds differently (the VAD probabilities move by fp32 rounding), the
-    separated signals are unchanged."""
-    import os
+    separated signals are unchanged. T = 126 at B = 9 and 1, T = 125 (odd) at B = 3, T = 11 (one k_istft_pair
+    workgroup per utterance) at B = 2."""
     from sep_tfanet_vad_amd import synth
     net = nets["with_vad"]
-    x = torch.from_numpy(synth.make_batch(9, 32000, 516)[0]).to(DEV)
-    a, va, ea, _ = _run(net, x, True)
-    os.environ["SEPVAD_VAD_FEAT"] = "1"
-    try:
-        b, vb, eb, _ = _run(net, x, True)
-    finally:
-        del os.environ["SEPVAD_VAD_FEAT"]
+    x = torch.from_numpy(synth.make_batch(B, N, 516)[0]).to(DEV)
+    assert torch.isfinite(x).all() and x.abs().max().item() > 0.5
+    monkeypatch.delenv("SEPVAD_VAD_FEAT", raising=False)
+    a, va, ea, used = _run(net, x, True)
+    assert used
+    monkeypatch.setenv("SEPVAD_VAD_FEAT", "1")
+    b, vb, eb, used = _run(net, x, True)
+    assert used
+    assert torch.isfinite(a).all() and torch.isfinite(va).all()
     assert (a - b).abs().max().item() <= 1e-6
     assert (va - vb).abs().max().item() <= 1e-5
     assert torch.equal(va >= 0.5, vb >= 0.5)
