@@ -1,17 +1,25 @@
 // C ABI of libsepvad.so (include/sepvad.h): weight folding/packing at create time and the
 // stream-ordered launch sequence of one SeparationModel.forward (reference model/model.py:402-461).
 //
-// Per forward (B utterances, T frames, 24 blocks):
-//   k_stft -> k_gate -> 24 x [ conv1d GEMM (loader: previous block's residual update)
-//                              -> k_dw_stats (d, split) -> res_out GEMM (reg2 folded into W / epilogue)
-//                              -> k_att_stats ]
-//   -> k_head_stats -> output GEMM (loader: residual update, PReLU, GN) -> k_vad1 -> k_istft
+// Per forward (B utterances, T frames, 24 blocks), the default fused flow (enqueue_chunk, fused_ok):
+//   k_stft_gate (STFT, activity gate, TCN input, TCN.LN records)
+//   -> k_tcn: the whole TCN and the output head (with the VAD conv1_1 tap products) as persistent launches
+//      (tcn_kernel.h), as many per forward as the epoch budget asks for; "big" launches are ordered across streams
+//   -> [k_vad_feat for T > 256] -> k_istft_pair (VAD tail, est = X * sigmoid(mask), iSTFT)
+// The fallback, the multi-kernel flow (SEPVAD_FUSED=0 / sepvad_set_fused(0), or an utterance whose group does not fit
+// the co-resident capacity or FG_MAX):
+//   k_stft_gate -> 24 x [ conv1d GEMM (loader: previous block's residual update)
+//                         -> k_dw_stats (d, split) -> res_out GEMM (reg2 folded into W / epilogue)
+//                         -> k_att_stats ]
+//   -> k_head_stats -> output GEMM (loader: residual update, PReLU, GN) -> k_vad1 -> k_istft_pair
+// The per-forward environment knobs (tests and diagnostics) are one table: KNOBS below.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
 #include "build/build_id.h"  // SEPVAD_BUILD_ID (Makefile: buildid.py)
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -466,6 +474,11 @@ GnSrc gn_src(const double* rec, int nrec, int rstride, int roff, const float* g,
   return s;
 }
 
+// The config's residual-LN mode as the kernels' LD_* code
+int ld_mode_of(const SepVadConfig& c) {
+  return c.ln_mode == SEPVAD_LN_RECURSIVE ? LD_RECURSIVE : (c.ln_mode == SEPVAD_LN_RESIDUAL ? LD_RESIDUAL : LD_ADD);
+}
+
 LoadSpec residual_spec(const sepvad_model* h, const Workspace& w, int i, const float* O, const float* R, int Tp) {
   LoadSpec ld{};
   ld.X = O; ld.X2 = R;
@@ -485,14 +498,20 @@ LoadSpec residual_spec(const sepvad_model* h, const Workspace& w, int i, const f
   return ld;
 }
 
+// A device copy of a host vector in a fresh allocation (*dst: freed with the handle)
+template <class T>
+hipError_t upload(T** dst, const std::vector<T>& src) {
+  const hipError_t e = hipMalloc(dst, src.size() * sizeof(T));
+  return e != hipSuccess ? e : hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
 // Weight/parameter blobs, hand-off buffers and residency capacity of the fused TCN (tcn_kernel.h):
 // per block the fragment-ordered fp16 hi/lo weights (WF_*) and one float parameter blob (PB_*), both
 // contiguous over blocks so the kernel addresses block i with uniform arithmetic (no pointer loads).
 int init_fused(sepvad_model* h, const Packer& pk) {
   int ncu = 0, dev = h->device;
   HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  const int ln = h->cfg.ln_mode == SEPVAD_LN_RECURSIVE ? LD_RECURSIVE
-                 : (h->cfg.ln_mode == SEPVAD_LN_RESIDUAL ? LD_RESIDUAL : LD_ADD);
+  const int ln = ld_mode_of(h->cfg);
   for (int p : {PREC_F16X3, PREC_F16, PREC_BF16, PREC_F32}) {
     // co-resident workgroups of the persistent TCN kernel that will run (both use one 512-thread workgroup per CU)
     h->tcn_cap_p[p] = ncu * tcn_blocks_per_cu(ln, p, 0, 1);
@@ -563,22 +582,14 @@ int init_fused(sepvad_model* h, const Packer& pk) {
     const int li = i % h->cfg.layer;
     if (bo.dil != (li == 0 ? 1 : (li % 4 + 1))) { g_err = "fused TCN: dilation schedule mismatch"; return SEPVAD_E_ARG; }
   }
-  HIPCHK(hipMalloc(&h->twf, wf.size() * sizeof(__half)));
-  HIPCHK(hipMemcpy(h->twf, wf.data(), wf.size() * sizeof(__half), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->twfq, wfq.size() * sizeof(__half)));
-  HIPCHK(hipMemcpy(h->twfq, wfq.data(), wfq.size() * sizeof(__half), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->twq[1], wq.size() * sizeof(__half)));
-  HIPCHK(hipMemcpy(h->twq[1], wq.data(), wq.size() * sizeof(__half), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->twq[2], wi.size() * sizeof(__half)));
-  HIPCHK(hipMemcpy(h->twq[2], wi.data(), wi.size() * sizeof(__half), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->twf16, ws16.size() * sizeof(__half)));
-  HIPCHK(hipMemcpy(h->twf16, ws16.data(), ws16.size() * sizeof(__half), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->twf32, wf32.size() * sizeof(float)));
-  HIPCHK(hipMemcpy(h->twf32, wf32.data(), wf32.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->twbf, wsbf.size() * sizeof(__half)));
-  HIPCHK(hipMemcpy(h->twbf, wsbf.data(), wsbf.size() * sizeof(__half), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->tprm, pb.size() * sizeof(float)));
-  HIPCHK(hipMemcpy(h->tprm, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(upload(&h->twf, wf));
+  HIPCHK(upload(&h->twfq, wfq));
+  HIPCHK(upload(&h->twq[1], wq));
+  HIPCHK(upload(&h->twq[2], wi));
+  HIPCHK(upload(&h->twf16, ws16));
+  HIPCHK(upload(&h->twf32, wf32));
+  HIPCHK(upload(&h->twbf, wsbf));
+  HIPCHK(upload(&h->tprm, pb));
   return SEPVAD_OK;
 }
 
@@ -590,7 +601,64 @@ void free_ctx(StreamCtx* c) {
   delete c;
 }
 
-int env_int(const char* name, int dflt);
+int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+
+// ---- The per-forward environment knobs ----
+// Read once per forward (read_knobs at the top of forward_impl; sepvad_fused_status reads them for its report) --
+// per forward, not per handle: the tests flip them between two forwards on one handle. None is needed in production.
+// Not here: the create-time knobs SEPVAD_SPLIT, SEPVAD_FUSED, SEPVAD_WLO (sepvad_create) and SEPVAD_MAX_STREAM_CTX
+// (get_ctx: sepvad_reserve reaches it outside a forward).
+constexpr int KNOB_UNSET = INT_MIN;
+constexpr int SALT_MAX = (int)((1u << (32 - TCN_EPOCH_BITS)) - 1);  // the largest launch salt (tag = salt << bits | epoch)
+struct Knobs {
+  int tcn_slices, tcn_wq16, tcn_xmode, tcn_align8, tcn_max_groups, tcn_max_iter, tcn_salt_max, tcn_force_giveup, tcn_delay,
+      vad_feat;
+  int tcn_spin_limit, tcn_nblk, tcn_dump_block, tcn_probe_warm, tcn_clock, tcn_info, giveup_info;
+  const char *tcn_probe, *tail_probe, *probe_block, *probe_out;
+};
+struct KnobDef {
+  const char* name;
+  int Knobs::*num;          // an integer knob (atoi of the value), or
+  const char* Knobs::*str;  // a string knob (nullptr when unset)
+  int dflt;
+};
+constexpr KnobDef KNOBS[] = {
+    // tests (tests/test_gpu_fused.py, tests/test_gpu_boundary.py set them between forwards)
+    {"SEPVAD_TCN_SLICES", &Knobs::tcn_slices, nullptr, 0},  // 1 | 2: force one- / two-slice workgroups (2 where it applies)
+    {"SEPVAD_TCN_WQ16", &Knobs::tcn_wq16, nullptr, 1},      // 0: two-slice launches stream the int8 lo bytes, not their fp16 copy
+    {"SEPVAD_TCN_XMODE", &Knobs::tcn_xmode, nullptr, 0},    // != 0: every hand-off store writes through (no same-XCD L2 path)
+    {"SEPVAD_TCN_ALIGN8", &Knobs::tcn_align8, nullptr, 0},  // 1: whole multiples of 8 groups per launch only
+    {"SEPVAD_TCN_MAX_GROUPS", &Knobs::tcn_max_groups, nullptr, 0},  // > 0: at most this many groups per launch
+    {"SEPVAD_TCN_MAX_ITER", &Knobs::tcn_max_iter, nullptr, 0},  // n: at most n utterances per group and launch
+    {"SEPVAD_TCN_SALT_MAX", &Knobs::tcn_salt_max, nullptr, SALT_MAX},  // the salt wraps here (clamped to 2 .. SALT_MAX)
+    {"SEPVAD_TCN_FORCE_GIVEUP", &Knobs::tcn_force_giveup, nullptr, 0},  // 1: report a give-up without one happening
+    {"SEPVAD_TCN_DELAY", &Knobs::tcn_delay, nullptr, 0},  // n: member 0 of every group sleeps n x ~8k cycles before its polls
+    {"SEPVAD_VAD_FEAT", &Knobs::vad_feat, nullptr, KNOB_UNSET},  // 1: k_vad_feat, 0: the tap sums in k_istft_pair; unset: T > 256
+    // diagnostics (tools/)
+    {"SEPVAD_TCN_SPIN_LIMIT", &Knobs::tcn_spin_limit, nullptr, 1 << 20},  // poll passes before a hand-off wait gives up
+    {"SEPVAD_TCN_NBLK", &Knobs::tcn_nblk, nullptr, 0},      // > 0: run only the first n blocks (wrong results)
+    {"SEPVAD_TCN_DUMP_BLOCK", &Knobs::tcn_dump_block, nullptr, 0},  // the block whose tensors sepvad_set_tcn_dump receives
+    {"SEPVAD_TCN_PROBE", nullptr, &Knobs::tcn_probe, 0},    // path: k_tcn phase stamps of the first launch (tools/tcn_probe.py)
+    {"SEPVAD_TCN_PROBE_WARM", &Knobs::tcn_probe_warm, nullptr, 0},  // 1: an unprobed launch before the probed one
+    {"SEPVAD_TCN_CLOCK", &Knobs::tcn_clock, nullptr, 0},    // 1: per-launch span and shader clock records (sepvad_tcn_clock)
+    {"SEPVAD_TCN_INFO", &Knobs::tcn_info, nullptr, 0},      // 1: print every k_tcn launch's shape to stderr
+    {"SEPVAD_GIVEUP_INFO", &Knobs::giveup_info, nullptr, 0},  // 1: print the first timed-out wait of a reported give-up
+    {"SEPVAD_TAIL_PROBE", nullptr, &Knobs::tail_probe, 0},  // path prefix: phase stamps of the tail kernels (tools/tail_probe.py)
+    {"SEPVAD_PROBE_BLOCK", nullptr, &Knobs::probe_block, 0},  // block index: GEMM wall-clock stamps of that block (tools/probe.py)
+    {"SEPVAD_PROBE_OUT", nullptr, &Knobs::probe_out, 0},    // path of the SEPVAD_PROBE_BLOCK dump
+};
+Knobs read_knobs() {
+  Knobs k{};
+  for (const KnobDef& d : KNOBS) {
+    if (d.num) k.*d.num = env_int(d.name, d.dflt);
+    else k.*d.str = getenv(d.name);
+  }
+  return k;
+}
+
 // The context of caller stream `stream` (created on first use; the caller holds h->mu).
 int get_ctx(sepvad_model* h, void* stream, StreamCtx** out) {
   for (auto& c : h->ctx)
@@ -632,15 +700,12 @@ int get_ctx(sepvad_model* h, void* stream, StreamCtx** out) {
   return SEPVAD_OK;
 }
 
-// Give-up words written by k_tcn launches of this context that completed since the last check: report
-// each once (the word holds the failing launch's salt, so a later give-up is a new value).
 // n consecutive hand-off tag salts for the k_tcn launches of one forward chunk: never 0, and never wrapping inside
 // the range (k_istft_pair poisons the outputs when the give-up word holds one of gsalt_lo .. gsalt_lo + n - 1). When
 // the 20-bit salt would wrap, the stream is drained and the hand-off words, the device give-up word and its host copy
 // restart from zero (a give-up not yet reported is kept in `pending`), so a reused salt never matches an old word.
-int salt_reserve(sepvad_model* h, StreamCtx* c, hipStream_t s, unsigned n, unsigned* lo) {
-  constexpr unsigned SMAX = (1u << (32 - TCN_EPOCH_BITS)) - 1;
-  const unsigned wrap_at = (unsigned)std::max(2, std::min((int)SMAX, env_int("SEPVAD_TCN_SALT_MAX", (int)SMAX)));
+int salt_reserve(sepvad_model* h, StreamCtx* c, hipStream_t s, const Knobs& kn, unsigned n, unsigned* lo) {
+  const unsigned wrap_at = (unsigned)std::max(2, std::min(SALT_MAX, kn.tcn_salt_max));
   if (n > wrap_at) return fail(SEPVAD_E_ARG, "fused TCN: too many launches in one forward");
   if (c->tsalt + n > wrap_at) {
     HIPCHK(hipStreamSynchronize(s));
@@ -657,8 +722,12 @@ int salt_reserve(sepvad_model* h, StreamCtx* c, hipStream_t s, unsigned n, unsig
   return SEPVAD_OK;
 }
 
-int check_giveup(StreamCtx* c) {
-  if (env_int("SEPVAD_GIVEUP_INFO", 0) && (c->pending != 0 || (c->herr[0] != 0 && c->herr[0] != c->reported))) {
+// Give-up words written by k_tcn launches of this context that completed since the last check: report
+// each once (the word holds the failing launch's salt, so a later give-up is a new value).
+int check_giveup(StreamCtx* c, const Knobs& kn) {
+  static const char* const msg = "fused TCN: a group hand-off wait gave up in an earlier forward on this stream "
+                                 "(that forward's outputs are invalid)";
+  if (kn.giveup_info && (c->pending != 0 || (c->herr[0] != 0 && c->herr[0] != c->reported))) {
     unsigned w[4] = {};  // diagnostics: {launch tag0, the timed-out wait's tag, its workgroup, its word index}
     if (hipMemcpy(w, c->terr, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess)
       fprintf(stderr, "sepvad: give-up on stream %p: tag0 %#x, first timed-out wait: tag %#x (salt %u epoch %u) "
@@ -671,14 +740,12 @@ int check_giveup(StreamCtx* c) {
   }
   if (c->pending != 0) {
     c->pending = 0;
-    return fail(SEPVAD_E_HIP, "fused TCN: a group hand-off wait gave up in an earlier forward on this stream "
-                              "(that forward's outputs are invalid)");
+    return fail(SEPVAD_E_HIP, msg);
   }
   const unsigned v = __atomic_load_n(c->herr, __ATOMIC_ACQUIRE);
   if (v != 0 && v != c->reported) {
     c->reported = v;
-    return fail(SEPVAD_E_HIP, "fused TCN: a group hand-off wait gave up in an earlier forward on this stream "
-                              "(that forward's outputs are invalid)");
+    return fail(SEPVAD_E_HIP, msg);
   }
   return SEPVAD_OK;
 }
@@ -1055,11 +1122,6 @@ bool fused_ok(const sepvad_model* h, int T) {
   return h->fused && G <= FG_MAX && tcn_cap_of(h) >= G;
 }
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // Progress of concurrent fused launches (include/sepvad.h: concurrent forwards on different streams are allowed).
 // A k_tcn group waits for all of its G members, and the grid is dealt in order, so a launch progresses as long as
 // 8 G of its workgroups are resident (tcn_kernel.h header). Two launches that each need more than half the chip for
@@ -1074,10 +1136,10 @@ int tcn2_cap_of(const sepvad_model* h) {
 // TcnSmem2) once one-slice workgroups would need more than one round of the chip (B * G > capacity), so every weight
 // fragment a CU streams feeds 64 frames instead of 32; the two give the same bits, so the choice never changes a
 // result. SEPVAD_TCN_SLICES = 1 | 2 forces one (2 where the two-slice kernel applies: G even, G <= FG_WAVE).
-int tcn_slices(const sepvad_model* h, int B, int G) {
+int tcn_slices(const sepvad_model* h, const Knobs& kn, int B, int G) {
   const int cap2 = tcn2_cap_of(h);
   if (G % 2 || G > FG_WAVE || cap2 < G / 2) return 1;
-  if (const int f = env_int("SEPVAD_TCN_SLICES", 0)) return f == 2 ? 2 : 1;
+  if (kn.tcn_slices) return kn.tcn_slices == 2 ? 2 : 1;
   const int per_round = std::max(1, tcn_cap_of(h) / G);  // utterances in one round of one-slice groups
   return B > per_round ? 2 : 1;
 }
@@ -1123,8 +1185,8 @@ struct TailProbe {
   hipStream_t s;
   std::string path;
   unsigned long long* buf = nullptr;
-  TailProbe(sepvad_model* h_, hipStream_t s_, const char* kernel) : h(h_), s(s_) {
-    const char* pre = getenv("SEPVAD_TAIL_PROBE");
+  TailProbe(sepvad_model* h_, hipStream_t s_, const Knobs& kn, const char* kernel) : h(h_), s(s_) {
+    const char* pre = kn.tail_probe;
     if (!pre) return;
     path = std::string(pre) + "." + kernel;
     if (!h->kprobe && hipMalloc(&h->kprobe, N * sizeof(unsigned long long)) != hipSuccess) return;
@@ -1162,7 +1224,7 @@ struct TraceRange {
 
 int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b0, int B, int N,
                   const SepVadOutputs* out, const SepVadInferKw* kw, hipStream_t s, TimingRec* tr,
-                  const XMap& xm) {
+                  const XMap& xm, const Knobs& kn) {
   const int T = 1 + N / HOP;
   const int Tp = round_up(T, TILE);
   const SepVadConfig& c = h->cfg;
@@ -1187,7 +1249,7 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
     sa.specdb = h->same_stft_window ? nullptr : w.specdb;
     sa.activity = c.activity_input; sa.gate_w = h->P(h->gate);
     sa.S0 = w.S0; sa.gate_rec = w.rec_gate;
-    TailProbe tp(h, s, "stft");
+    TailProbe tp(h, s, kn, "stft");
     sa.probe = tp.buf;
     HIPCHK(launch_stft_gate(sa, s));
     HIPCHK(tp.dump(B, Tp / (2 * GATE_ROWS)));  // k_stft_gate's grid (32 own frames)
@@ -1211,14 +1273,14 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
   const bool vad_in_head = use_fused && has_vad && !c.final_vad_masked_speakers;
   if (use_fused) {
     // persistent launches of the whole TCN (tcn_kernel.h), the output head inside them
-    const int nsl = h->tdump ? 1 : tcn_slices(h, B, G);  // (the parity-dump instantiation is one-slice only)
+    const int nsl = h->tdump ? 1 : tcn_slices(h, kn, B, G);  // (the parity-dump instantiation is one-slice only)
     const int cap = nsl == 2 ? tcn2_cap_of(h) : tcn_cap_of(h);
     h->last_nsl = nsl;
     const int Gt = G / nsl;  // workgroups per utterance
     TcnArgs ta{};
     ta.T = T; ta.Tp = Tp; ta.G = G; ta.nsl = nsl; ta.nblk = h->nblk; ta.layer = c.layer;
-    if (const int nb = env_int("SEPVAD_TCN_NBLK", 0); nb > 0 && nb < h->nblk) ta.nblk = nb;  // diagnostics: truncated stack
-    ta.ln_mode = c.ln_mode == SEPVAD_LN_RECURSIVE ? LD_RECURSIVE : (c.ln_mode == SEPVAD_LN_RESIDUAL ? LD_RESIDUAL : LD_ADD);
+    if (const int nb = kn.tcn_nblk; nb > 0 && nb < h->nblk) ta.nblk = nb;  // diagnostics: truncated stack
+    ta.ln_mode = ld_mode_of(c);
     ta.tf_att = c.tf_attention;
     ta.prec = h->prec;
     ta.lo8 = h->prec == PREC_F16X3 ? h->lo8 : 0;
@@ -1230,16 +1292,16 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
     ta.inv_hid = 1.0 / ((double)HID * T);
     ta.alpha_h = h->out_a;
     ta.gran = cx->tgran; ta.err = cx->terr; ta.herr = cx->herr_dev;
-    ta.xmode = env_int("SEPVAD_TCN_XMODE", 0);
+    ta.xmode = kn.tcn_xmode;
     auto launch_t = [&](const TcnArgs& t, int grid) { return launch_tcn(t, grid, s); };
-    ta.spin_limit = (unsigned)env_int("SEPVAD_TCN_SPIN_LIMIT", 1 << 20);
-    ta.force_err = env_int("SEPVAD_TCN_FORCE_GIVEUP", 0);
-    ta.dbg_delay = (unsigned)std::max(0, env_int("SEPVAD_TCN_DELAY", 0));
-    ta.dump_blk = std::max(0, std::min(h->nblk - 1, env_int("SEPVAD_TCN_DUMP_BLOCK", 0)));
+    ta.spin_limit = (unsigned)kn.tcn_spin_limit;
+    ta.force_err = kn.tcn_force_giveup;
+    ta.dbg_delay = (unsigned)std::max(0, kn.tcn_delay);
+    ta.dump_blk = std::max(0, std::min(h->nblk - 1, kn.tcn_dump_block));
     // every group the chip holds (the kernel puts the groups of 8 * Gt * floor(groups / 8) blocks on one XCD each and the
     // rest, fewer than 8, on consecutive blocks; SEPVAD_TCN_ALIGN8=1: whole multiples of 8 groups only, as in round 4)
     int ngroups = std::min(B, cap / Gt);
-    if (ngroups >= 8 && env_int("SEPVAD_TCN_ALIGN8", 0)) ngroups -= ngroups % 8;
+    if (ngroups >= 8 && kn.tcn_align8) ngroups -= ngroups % 8;
     // the output head, inside k_tcn after each utterance's last block (its lo plane in the blocks' format)
     ta.hg = h->P(h->out_g); ta.hbe = h->P(h->out_b); ta.hsx = h->out_sx;
     ta.hwh = h->prec == PREC_F32 ? reinterpret_cast<const __half*>(h->P(h->wout_spk.ff32))
@@ -1248,10 +1310,7 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
     // two slices, int8 lo plane: the same lo values streamed as fp16 (no widening VALU beside the MFMAs; at two slices
     // the weight stream is not the bound). Bitwise equal to the int8 kernel: its widening is exact (tcn_common.h
     // lo8_widen), so both feed the MFMAs the same fp16 operands. SEPVAD_TCN_WQ16=0: the int8 kernel.
-    // SEPVAD_TCN_WQ16=2: one-slice launches too (A/B)
-    const int wq16 = env_int("SEPVAD_TCN_WQ16", 1);
-    if (ta.lo8 == 2 && ((nsl == 2 && wq16 >= 1 && h->tcn2_cap_p[PREC_F16X3] >= cap) ||
-                        (nsl == 1 && wq16 >= 2 && h->tcn_cap_p[PREC_F16X3] >= cap))) {
+    if (ta.lo8 == 2 && nsl == 2 && kn.tcn_wq16 >= 1 && h->tcn2_cap_p[PREC_F16X3] >= cap) {
       ta.lo8 = 0;
       ta.wfrag = h->twfq;
       ta.hwl = h->H(h->wout_spk.fq);
@@ -1266,11 +1325,11 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
     }
     // diagnostics (SEPVAD_TCN_MAX_GROUPS): fewer groups per launch, so each loops over more utterances (tests reach
     // the epoch budget below with small batches)
-    if (const int mg = env_int("SEPVAD_TCN_MAX_GROUPS", 0); mg > 0 && mg < ngroups) ngroups = mg;
+    if (const int mg = kn.tcn_max_groups; mg > 0 && mg < ngroups) ngroups = mg;
     // groups above 32 members (whole files, one slice): XCD runs (tcn_kernel.h RUN: R = ceil(G / 8) consecutive members
-    // per XCD, a group on 8 R blocks), where that costs this batch no group of the round; SEPVAD_TCN_RUNS=0: off
+    // per XCD, a group on 8 R blocks), where that costs this batch no group of the round
     ta.run = 0;
-    if (nsl == 1 && G > 32 && env_int("SEPVAD_TCN_RUNS", 1)) {
+    if (nsl == 1 && G > 32) {
       const int R = (G + 7) / 8;
       if (std::min(B, cap / (8 * R)) >= ngroups) ta.run = R;
     }
@@ -1281,16 +1340,16 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
     // (SEPVAD_TCN_MAX_ITER lowers it: tests force several launches per forward)
     const int ep_utt = 4 * h->nblk + 1;
     int max_iter = ((1 << TCN_EPOCH_BITS) - 2) / ep_utt;
-    if (const int mi = env_int("SEPVAD_TCN_MAX_ITER", 0)) max_iter = std::min(max_iter, mi);
+    if (const int mi = kn.tcn_max_iter) max_iter = std::min(max_iter, mi);
     if (max_iter < 1) return fail(SEPVAD_E_ARG, "fused TCN: too many blocks");
     if (1 + (long long)max_iter * ep_utt >= (1 << TCN_EPOCH_BITS)) return fail(SEPVAD_E_ARG, "fused TCN: epoch budget");
     const int per_launch = max_iter * ngroups;
-    const char* probe_path = getenv("SEPVAD_TCN_PROBE");
+    const char* probe_path = kn.tcn_probe;
     const size_t probe_n = (size_t)h->tcn_cap * h->nblk * 16 * 9;  // wave-0 region + per-wave region
     // this chunk's launch salts, reserved as one range (salt_reserve: never 0, no wrap inside the range)
-    const bool warm = probe_path && env_int("SEPVAD_TCN_PROBE_WARM", 0);
+    const bool warm = probe_path && kn.tcn_probe_warm;
     {
-      const int rc = salt_reserve(h, cx, s, (unsigned)((B + per_launch - 1) / per_launch + (warm ? 1 : 0)), &gsalt_lo);
+      const int rc = salt_reserve(h, cx, s, kn, (unsigned)((B + per_launch - 1) / per_launch + (warm ? 1 : 0)), &gsalt_lo);
       if (rc) return rc;
     }
     gsalt_n = 0;
@@ -1318,7 +1377,7 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
         }
       }
       ta.clk = nullptr;
-      if (env_int("SEPVAD_TCN_CLOCK", 0)) {  // diagnostics: per-launch span and shader clock (sepvad_tcn_clock)
+      if (kn.tcn_clock) {  // diagnostics: per-launch span and shader clock (sepvad_tcn_clock)
         if (!h->tclk) {
           HIPCHK(hipMalloc(&h->tclk, (size_t)TCLK_RECS * 8 * sizeof(unsigned long long)));
           HIPCHK(hipMemset(h->tclk, 0, (size_t)TCLK_RECS * 8 * sizeof(unsigned long long)));
@@ -1326,11 +1385,11 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
         ta.clk = h->tclk + (size_t)(h->tclk_n++ % TCLK_RECS) * 8;
         HIPCHK(hipMemsetAsync(ta.clk, 0, 8 * sizeof(unsigned long long), s));
       }
-      if (env_int("SEPVAD_TCN_INFO", 0))  // diagnostics: the persistent launch's shape
+      if (kn.tcn_info)  // diagnostics: the persistent launch's shape
         fprintf(stderr, "sepvad: k_tcn grid=%d G=%d slices=%d groups=%d B=%d capacity=%d run=%d\n", ngl * gstride, G, nsl, ngl,
                 Bl, cap, ta.run);
-      const bool big = tcn_big(cap, gstride) && !env_int("SEPVAD_TCN_NO_ORDER", 0);
-      TailProbe thp(h, s, "tcnhead");
+      const bool big = tcn_big(cap, gstride);
+      TailProbe thp(h, s, kn, "tcnhead");
       ta.hprobe = u0 == 0 ? thp.buf : nullptr;
       auto run = [&]() -> int {
         if (ev()) return SEPVAD_E_HIP;
@@ -1422,7 +1481,7 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
 
       AttStatsArgs at{};
       at.B = B; at.T = T; at.Tp = Tp; at.mtiles = CH / TILE; at.ntiles = ntu; at.tf_att = c.tf_attention;
-      at.ln_mode = c.ln_mode == SEPVAD_LN_RECURSIVE ? LD_RECURSIVE : (c.ln_mode == SEPVAD_LN_RESIDUAL ? LD_RESIDUAL : LD_ADD);
+      at.ln_mode = ld_mode_of(c);
       at.R = w.R; at.O = w.O[cur]; at.colsum = w.colsum; at.rowsum = w.rowsum; at.attp = h->P(bo.attp);
       if (c.ln_mode == SEPVAD_LN_RECURSIVE) { at.ga = h->P(bo.lna_g); at.bea = h->P(bo.lna_b); }
       at.at = w.at; at.af = w.af; at.out_rec = w.rec_mom;
@@ -1460,7 +1519,7 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
   // whole-utterance BN_1 sums are 2 items per thread (cfg 2: +0.4 %, 152.4k vs 151.9k utt/s interleaved,
   // profiles/r06pv/vadfeat_lines.txt; round 2 had measured equal, profiles/r02av_ab_vadfeat.txt); longer utterances
   // keep k_vad_feat (each of the T / 11 workgroups would sum all 4 T items).
-  const bool vad_taps_in_istft = vad_in_head && !env_int("SEPVAD_VAD_FEAT", T > 256 ? 1 : 0);
+  const bool vad_taps_in_istft = vad_in_head && !(kn.vad_feat == KNOB_UNSET ? (T > 256 ? 1 : 0) : kn.vad_feat);
   if (vad_in_head && !vad_taps_in_istft) {
     VadFeatArgs vf{};
     vf.B = B; vf.T = T; vf.Tp = Tp; vf.vP = w.vP;
@@ -1476,7 +1535,7 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
     v.masks = w.masks; v.X = w.X;
     v.w1 = h->P(h->v_w1); v.b1 = h->P(h->v_b1); v.alpha = h->v_a;
     v.vy = w.vy; v.out_rec = w.rec_vad;
-    TailProbe tp(h, s, "vad1");
+    TailProbe tp(h, s, kn, "vad1");
     v.probe = tp.buf;
     HIPCHK(launch_vad1(v, s));
     HIPCHK(tp.dump(B * 2, Tp / VAD_ROWS));
@@ -1506,7 +1565,7 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
     is.mask_out = out->mask ? out->mask + u2 * NBIN * T : nullptr;
     is.y = out->sep + u2 * N;
     if (use_fused && gsalt_n > 0) { is.gerr = cx->terr; is.gsalt_lo = gsalt_lo; is.gsalt_n = gsalt_n; }
-    TailProbe tp(h, s, "istft");
+    TailProbe tp(h, s, kn, "istft");
     is.probe = tp.buf;
     HIPCHK(launch_istft_pair(is, s));
     HIPCHK(tp.dump(B, (T + 10) / 11));  // k_istft_pair's grid (IP_OWN = 11)
@@ -1518,10 +1577,11 @@ int forward_impl(sepvad_model* h, const float* x, int ldx, int B, int N, const S
                  const SepVadInferKw* kw, hipStream_t s, const XMap& xm = XMap()) {
   const int T = 1 + N / HOP;
   const int Tp = round_up(T, TILE);
+  const Knobs kn = read_knobs();  // every per-forward environment knob, read once
   StreamCtx* cx = nullptr;
   int rc = get_ctx(h, (void*)s, &cx);
   if (rc) return rc;
-  rc = check_giveup(cx);  // an earlier forward on this stream whose k_tcn gave up: report it now
+  rc = check_giveup(cx, kn);  // an earlier forward on this stream whose k_tcn gave up: report it now
   if (rc) return rc;
   rc = ws_reserve(cx, B, N);
   if (rc) return rc;
@@ -1532,7 +1592,7 @@ int forward_impl(sepvad_model* h, const float* x, int ldx, int B, int N, const S
   h->ev.clear();
   // diagnostics probe (single chunk only)
   h->probe_blk = -1;
-  if (const char* pb = getenv("SEPVAD_PROBE_BLOCK")) {
+  if (const char* pb = kn.probe_block) {
     const size_t need = 2 * (size_t)B * (Tp / TILE) * (CH / TILE) * PROBE_SLOTS;
     if (need > h->probe_n) {
       if (h->probe) (void)hipFree(h->probe);
@@ -1549,7 +1609,7 @@ int forward_impl(sepvad_model* h, const float* x, int ldx, int B, int N, const S
   TimingRec tr;
   if (nsplit == 1) {
     if (ev_record(h, s)) return SEPVAD_E_HIP;
-    rc = enqueue_chunk(h, cx, x, ldx, 0, B, N, out, kw, s, h->timing || h->probe_blk >= 0 ? &tr : nullptr, xm);
+    rc = enqueue_chunk(h, cx, x, ldx, 0, B, N, out, kw, s, h->timing || h->probe_blk >= 0 ? &tr : nullptr, xm, kn);
     if (rc) return rc;
     if (ev_record(h, s)) return SEPVAD_E_HIP;
   } else {
@@ -1559,7 +1619,7 @@ int forward_impl(sepvad_model* h, const float* x, int ldx, int B, int N, const S
     for (int k = 0; k < nsplit; ++k) {
       const int bc = B / nsplit + (k < B % nsplit ? 1 : 0);
       HIPCHK(hipStreamWaitEvent(h->sub[k], h->fork, 0));
-      rc = enqueue_chunk(h, cx, x, ldx, b0, bc, N, out, kw, h->sub[k], nullptr, xm);
+      rc = enqueue_chunk(h, cx, x, ldx, b0, bc, N, out, kw, h->sub[k], nullptr, xm, kn);
       HIPCHK(hipEventRecord(h->join[k], h->sub[k]));
       HIPCHK(hipStreamWaitEvent(s, h->join[k], 0));
       if (rc) return rc;
@@ -1577,7 +1637,7 @@ int forward_impl(sepvad_model* h, const float* x, int ldx, int B, int N, const S
     h->g2_launches = (int)tr.g2_ev.size();
   }
   if (h->probe && h->probe_blk >= 0) {
-    const char* path = getenv("SEPVAD_PROBE_OUT");
+    const char* path = kn.probe_out;
     const size_t g1_grid = (size_t)B * (Tp / TILE) * (CH / TILE);
     std::vector<unsigned long long> hp(2 * g1_grid * PROBE_SLOTS);
     HIPCHK(hipStreamSynchronize(s));
@@ -1656,9 +1716,10 @@ int32_t sepvad_fused_status(sepvad_handle h, int32_t* used) {
   std::lock_guard<std::mutex> lk(h->mu);
   if (used) *used = h->last_fused ? h->last_nsl : 0;
   HIPCHK(hipDeviceSynchronize());
+  const Knobs kn = read_knobs();
   int rc = SEPVAD_OK;
   for (auto& c : h->ctx) {
-    const int r = check_giveup(c.get());
+    const int r = check_giveup(c.get(), kn);
     if (r && rc == SEPVAD_OK) rc = r;
   }
   return rc;

@@ -24,9 +24,6 @@ __device__ __forceinline__ Tp* uni(Tp* p) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
   return (Tp*)(((unsigned long long)hi << 32) | lo);
 }
-__device__ __forceinline__ float unif(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
-}
 // Buffer descriptor over a wave-uniform base. The base goes through readfirstlane: under SGPR pressure
 // hipcc keeps uniform pointers in VGPRs, and a descriptor it cannot prove uniform turns every buffer
 // access into a waterfall loop (cdna_hip_programming.md T20).
@@ -50,12 +47,6 @@ __device__ __forceinline__ void gputd(u64* p, unsigned tag, double v, bool l2) {
   gput(p, tag, (unsigned)b, l2);
   gput(p + 1, tag, (unsigned)(b >> 32), l2);
 }
-__device__ __forceinline__ double dword2(unsigned lo, unsigned hi) {
-  return __builtin_bit_cast(double, ((u64)hi << 32) | lo);
-}
-#ifndef TCN_POLL_SERIAL
-#define TCN_POLL_SERIAL 0
-#endif
 #ifndef TCN_POLL_SLEEP
 #define TCN_POLL_SLEEP 1  // s_sleep between poll passes (units of 64 clocks; 0 = none)
 #endif
@@ -82,17 +73,8 @@ __device__ __forceinline__ void gpollt(const u64* const (&p)[N], const unsigned 
   unsigned spins = 0;
   for (;;) {
     u64 x[N];
-#if TCN_POLL_SERIAL  // A/B switch: the round-2 form (each load inside its own `if (p[k])`: one round trip per word)
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      x[k] = 0;
-      if (p[k] != nullptr) x[k] = __hip_atomic_load(p[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    (void)dummy;
-#else
 #pragma unroll
     for (int k = 0; k < N; ++k) x[k] = __hip_atomic_load(p[k] != nullptr ? p[k] : dummy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -196,27 +178,8 @@ __device__ __forceinline__ void split_store(_Float16* hi, _Float16* lo, int idx,
   }
 }
 
-// two adjacent values (idx even): one 32-bit LDS store per plane
-template <int PRE>
-__device__ __forceinline__ void split_store2(_Float16* hi, _Float16* lo, int idx, float v0, float v1) {
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  if constexpr (PRE == PREC_F16X3) {
-    const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-    *reinterpret_cast<f16x2*>(hi + idx) = f16x2{h0, h1};
-    *reinterpret_cast<f16x2*>(lo + idx) = f16x2{(_Float16)(v0 - (float)h0), (_Float16)(v1 - (float)h1)};
-  } else if constexpr (PRE == PREC_F16) {
-    *reinterpret_cast<f16x2*>(hi + idx) = f16x2{(_Float16)v0, (_Float16)v1};
-  } else {
-    *reinterpret_cast<bf16x2*>(hi + idx) = bf16x2{(__bf16)v0, (__bf16)v1};
-  }
-}
-
 // ---- packed fp32 (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32: two channels per instruction) ----
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef TCN_MIX
-#define TCN_MIX 1  // round 6: lo parts by v_fma_mix (bitwise equal, -0.5 % k_tcn cycles, profiles/r06mix/)
-#endif
 // The fp16 lo parts of a pair, (f16)(v - (float)h) with hb = the pair's hi halves, as two v_fma_mix (hi read as f16,
 // the difference rounded to f16 once): v - h is exact in fp32 (h is v rounded to fp16), so the bits equal the
 // convert / subtract / convert form, in 2 instructions instead of 5. Inline asm (no builtin); the closing s_nop 1 covers
@@ -253,14 +216,8 @@ __device__ __forceinline__ void store_d4(_Float16* hi, _Float16* lo, f32x2 y0, f
   if constexpr (PRE == PREC_F16X3) {
     const f16x2v ha = __builtin_convertvector(a, f16x2v), hb = __builtin_convertvector(b, f16x2v);
     *reinterpret_cast<u32x2v*>(hi) = u32x2v{__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb)};
-    if constexpr (TCN_MIX) {
-      *reinterpret_cast<u32x2v*>(lo) = u32x2v{lo_pair_mix(a, __builtin_bit_cast(unsigned, ha)),
-                                              lo_pair_mix(b, __builtin_bit_cast(unsigned, hb))};
-      return;
-    }
-    const f16x2v la = __builtin_convertvector(a - __builtin_convertvector(ha, f32x2), f16x2v);
-    const f16x2v lb = __builtin_convertvector(b - __builtin_convertvector(hb, f32x2), f16x2v);
-    *reinterpret_cast<u32x2v*>(lo) = u32x2v{__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb)};
+    *reinterpret_cast<u32x2v*>(lo) = u32x2v{lo_pair_mix(a, __builtin_bit_cast(unsigned, ha)),
+                                            lo_pair_mix(b, __builtin_bit_cast(unsigned, hb))};
   } else if constexpr (PRE == PREC_F16) {
     const f16x2v ha = __builtin_convertvector(a, f16x2v), hb = __builtin_convertvector(b, f16x2v);
     *reinterpret_cast<u32x2v*>(hi) = u32x2v{__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb)};
@@ -269,32 +226,15 @@ __device__ __forceinline__ void store_d4(_Float16* hi, _Float16* lo, f32x2 y0, f
     *reinterpret_cast<u32x2v*>(hi) = u32x2v{__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb)};
   }
 }
-// Two values of one channel at two frames (LDS rows idx and idx + ld) in the PRE format of split_store
-template <int PRE>
-__device__ __forceinline__ void split_store_rows(_Float16* hi, _Float16* lo, int idx, int ld, f32x2 v) {
-  if constexpr (PRE == PREC_F16X3) {
-    const f16x2v h = __builtin_convertvector(v, f16x2v);
-    const f16x2v l = __builtin_convertvector(v - __builtin_convertvector(h, f32x2), f16x2v);
-    hi[idx] = h.x; hi[idx + ld] = h.y;
-    lo[idx] = l.x; lo[idx + ld] = l.y;
-  } else if constexpr (PRE == PREC_F16) {
-    const f16x2v h = __builtin_convertvector(v, f16x2v);
-    hi[idx] = h.x; hi[idx + ld] = h.y;
-  } else if constexpr (PRE == PREC_F32) {  // (idx, ld in floats)
-    reinterpret_cast<float*>(hi)[idx] = v.x; reinterpret_cast<float*>(hi)[idx + ld] = v.y;
-  } else {
-    const bf16x2v h = __builtin_convertvector(v, bf16x2v);
-    reinterpret_cast<__bf16*>(hi)[idx] = h.x; reinterpret_cast<__bf16*>(hi)[idx + ld] = h.y;
-  }
-}
-// split_store_rows with the lane pair (2c, 2c+1) packing its two channels into 32-bit stores: the even lane writes
-// channels (m, m+1) of frame tl, the odd lane channels (m-1, m) of frame tl+1, each taking the partner's 16-bit value
-// through one DPP swap (quad_perm [1,0,3,2]) and one v_perm: half the LDS store instructions of split_store_rows.
-// idx = the lane's element for frame tl (as split_store_rows); every lane of the wave must take part (DPP).
+// Two values of one channel at two frames (LDS rows idx and idx + ld) in the PRE format of split_store, the lane pair
+// (2c, 2c+1) packing its two channels into 32-bit stores: the even lane writes channels (m, m+1) of frame tl, the odd
+// lane channels (m-1, m) of frame tl+1, each taking the partner's 16-bit value through one DPP swap (quad_perm
+// [1,0,3,2]) and one v_perm: half the LDS store instructions of one 16-bit store per value.
+// idx = the lane's element for frame tl; every lane of the wave must take part (DPP).
 template <int PRE>
 __device__ __forceinline__ void split_store_rows_pk(_Float16* hi, _Float16* lo, int idx, int ld, f32x2 v, bool odd) {
   if constexpr (PRE == PREC_F32) {  // 32-bit values already: plain stores (idx, ld in floats)
-    split_store_rows<PRE>(hi, lo, idx, ld, v);
+    reinterpret_cast<float*>(hi)[idx] = v.x; reinterpret_cast<float*>(hi)[idx + ld] = v.y;
     return;
   }
   const unsigned sel = odd ? 0x03020706u : 0x05040100u;  // odd: {partner.y, own.y}; even: {own.x, partner.x}
@@ -306,12 +246,7 @@ __device__ __forceinline__ void split_store_rows_pk(_Float16* hi, _Float16* lo, 
   if constexpr (PRE == PREC_F16X3) {
     const f16x2v h = __builtin_convertvector(v, f16x2v);
     put(hi, __builtin_bit_cast(unsigned, h));
-    if constexpr (TCN_MIX) {
-      put(lo, lo_pair_mix(v, __builtin_bit_cast(unsigned, h)));
-      return;
-    }
-    const f16x2v l = __builtin_convertvector(v - __builtin_convertvector(h, f32x2), f16x2v);
-    put(lo, __builtin_bit_cast(unsigned, l));
+    put(lo, lo_pair_mix(v, __builtin_bit_cast(unsigned, h)));
   } else if constexpr (PRE == PREC_F16) {
     put(hi, __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2v)));
   } else {
@@ -437,12 +372,6 @@ __device__ __forceinline__ float rs16_wave(float (&x)[16], int lane) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4e, 0xf, 0xf, false));
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xb1, 0xf, 0xf, false));
   return v;
-}
-// Sum over the 64 lanes (+ row_bcast:31), returned wave-uniform (lane 63).
-__device__ __forceinline__ float wave_total(float v) {
-  v = half_total(v);
-  v += dpp_f<0x143>(v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 __device__ __forceinline__ double readlane_d(double v, int l) {
   const u64 b = __builtin_bit_cast(u64, v);

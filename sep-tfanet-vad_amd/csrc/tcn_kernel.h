@@ -47,53 +47,8 @@
 
 namespace sepvad {
 
-// A/B switches (tools/build_variants.sh builds one library per setting; the losing alternatives of rounds 2-3 --
-// scalar elementwise phases, separate P2 round, thread-finished GN moments, double GN finish, 11-term moments, burst
-// ring prefetch, LDS epilogue parameters -- live in the git history)
-#ifndef TCN_PRIO
-// 1 (round 5): waves 4-7 at s_setprio 1 for the whole kernel (MI355X_MICROARCH.md "Static priority for the younger
-// half"): they share each SIMD's MFMA pipe with waves 0-3 and, without it, finish every GEMM last (the barrier after
-// the GEMM waits for them): k_tcn -2.4 % shader cycles at cfg 2, bitwise equal (profiles/r05_prio/). 0 = round 4.
-#define TCN_PRIO 1
-#endif
-#ifndef TCN_FULLM
-// 1 (round 6): row loops without the frame masks where a workgroup's frames are all inside [0, T) (a second copy of
-// each loop, taken by a uniform branch); bitwise neutral; with it the two-slice kernels compile without spills
-#define TCN_FULLM 1
-#endif
-#ifndef TCN_FULLDW
-#define TCN_FULLDW 1  // TCN_FULLM for the depthwise conv too (a second copy of its 4 dilation variants)
-#endif
-#ifndef TCN_BSRED
-// 1 (round 6): block_sums of more than 4 values (the moment record): reduce-scatters (rs16_wave) instead of DPP chains
-#define TCN_BSRED 1
-#endif
-#ifndef TCN_RSRED
-// 1 (round 6): row / frame sums: one reduce-scatter over the 32-lane halves (rs16_half) instead of 16 DPP chains of 5
-// (the removal probe TCN_DIAG=3 put those chains at 2.9 % of k_tcn's cycles); with TCN_BSRED and TCN_FULLM cfg 2 +3 %,
-// cfg 5 +7.8 % (profiles/r06w2/)
-#define TCN_RSRED 1
-#endif
-#ifndef TCN_WPIPE
-// 1 (round 6): the byte lo plane's widening one K step ahead (wave_gemm): -0.2 % k_tcn cycles at cfg 2, bitwise equal
-// (profiles/r06a/cyc.txt)
-#define TCN_WPIPE 1
-#endif
-#ifndef TCN_A1V
-// 1 (round 6): conv1d PReLU slope a1 in a VGPR, not readfirstlane'd (hipcc hoisted that into the GEMM's first K step,
-// whose vmcnt wait then also waited for the block-parameter loads): -0.5 % cycles, with TCN_WPIPE -0.7 %, bitwise equal
-#define TCN_A1V 1
-#endif
-#ifndef TCN_PP
-// 1 (round 6, measured, not kept): one-slice depthwise conv + res_out GEMM as a wave-role ping-pong. Waves 4-7 (s_setprio
-// 1) compute the first K half of d (input channels 0..127) and start their res_out MFMAs on it while waves 0-3 compute the
-// second half on the same SIMDs; waves 0-3 then run their whole K, waves 4-7 the second half. Hand-over by two LDS
-// counters (no workgroup barrier); the same d, the same K order, the GN2 wave totals in the plain mapping's order: the
-// same bits (digests equal at cfg 2 and cfg 5). Waves 0-3's half of d slows from 2.16 to 2.44 us beside the MFMAs and
-// their 32 K steps still take 4.0 us, so the pair of phases shrinks by 0.2 us per block only, while the kernel spills 29
-// VGPRs around its prologue and head: k_tcn +2.4 % cycles at cfg 2 (profiles/r06pp/).
-#define TCN_PP 0
-#endif
+// Still switchable at compile time: the numeric tunables TCN_PD, TCN_PDQ, TCN_POLL_SLEEP (tools/build_variants.sh) and the
+// diagnostic / census builds TCN_DIAG, TCN_SUB, TCN_MARK, TCN_CENSUS_DIL, TCN_ONE. Every retired A/B switch: DESIGN.md §4a.
 #ifndef TCN_SUB
 #define TCN_SUB 0    // probe sub-stamps 13/14: 0 in the x' update, 1 in the depthwise conv (diagnostics)
 #endif
@@ -111,14 +66,7 @@ constexpr int LDDF = HID + 4;
 #endif
 constexpr int PD = TCN_PD;        // weight K steps in flight per wave
 #ifndef TCN_DIAG
-#define TCN_DIAG 0   // diagnostics only (wrong results): 1 = GEMM ring refills skipped, 2 = GEMM MFMAs skipped,
-                     // 3 = the frame sums' DPP reductions skipped (VALU-removal probe)
-#endif
-#ifndef TCN_AD
-#define TCN_AD 1     // GEMM A-fragment LDS reads issued this many K steps ahead (2: no gain, profiles/r03h_ab_*)
-#endif
-#ifndef TCN_XPK
-#define TCN_XPK 1    // x' update: lane pairs pack two channels per 32-bit LDS store (1) or 16-bit stores (0)
+#define TCN_DIAG 0   // diagnostics only (wrong results): 1 = GEMM ring refills skipped, 2 = GEMM MFMAs skipped
 #endif
 #ifndef TCN_PDQ
 #define TCN_PDQ 8    // ... with the e4m3 lo plane (16 fits the registers, 238 VGPRs, but measured 4 % more cycles)
@@ -150,8 +98,6 @@ struct TcnSmem {
   unsigned gw[GW_WORDS] __attribute__((aligned(8)));  // gathered statistic words (GN words, moment records)
   double dred[16];
   float prm[PB_SIZE];             // this block's parameter blob (PB_*)
-  float pps[16];                  // TCN_PP: the GN2 wave totals {sum [8], sumsq [8]}
-  unsigned ppc[2];                // TCN_PP: waves done with K half 0 / 1 of d (4 per block)
 };
 static_assert(offsetof(TcnSmem, Alo) == offsetof(TcnSmem, Ahi) + sizeof(TcnSmem::Ahi) &&
               16 * FR * HEAD_VAD_N * 4 <= sizeof(TcnSmem::H) && 4 * FR * 32 * 2 <= FR * (LDD - LDX) &&
@@ -268,9 +214,7 @@ __device__ __forceinline__ void wave_gemm_f32(f32x16v (&acc)[NT], const float* A
   for (int i = 0; i < RD; ++i) step(NS - RD + i, i, false);
 }
 
-// CONT: the ring keeps streaming past the last step (steps KS0 + NS .. KS0 + NS + RD - 1 in flight on return, for a
-// following call with KS0 + NS)
-template <int NS, int LDA, int PRE, int RD = PD, int LQ = 0, int NT = 1, int KS0 = 0, bool CONT = false>
+template <int NS, int LDA, int PRE, int RD = PD, int LQ = 0, int NT = 1, int KS0 = 0>
 __device__ __forceinline__ void wave_gemm(f32x16v (&acc)[NT], const _Float16* Ahi, const _Float16* Alo,
                                           __amdgpu_buffer_rsrc_t wh, __amdgpu_buffer_rsrc_t wl, int voff, int voffl,
                                           u32x4v (&rh)[RD], u32x4v (&rl)[RD], int lane) {
@@ -284,11 +228,10 @@ __device__ __forceinline__ void wave_gemm(f32x16v (&acc)[NT], const _Float16* Ah
   static_assert(!L8 || (PRE == PREC_F16X3 && RD % 2 == 0), "byte lo plane: F16X3, K-step pairs");
   constexpr bool X3 = PRE == PREC_F16X3;
   const int aoff = (lane & 31) * LDA + 8 * (lane >> 5);
-  // A fragments AD steps ahead: the LDS reads of step s+AD are in flight during steps s..s+AD-1 (AD = 2: a wave that
-  // has the SIMD's matrix pipe to itself -- the other wave of the SIMD done with its GEMM -- issues a step every ~96
-  // cycles, shorter than an LDS read under load)
-  constexpr int AD = TCN_AD;
-  static_assert(AD >= 1, "A-read depth");
+  // A fragments AD steps ahead: the LDS reads of step s+AD are in flight during steps s..s+AD-1 (AD = 2 -- for a wave
+  // that has the SIMD's matrix pipe to itself and issues a step every ~96 cycles, shorter than an LDS read under load --
+  // measured no gain, profiles/r03h_ab_*)
+  constexpr int AD = 1;
   f16x8 aH[AD + 1][NT], aL[AD + 1][NT];
 #pragma unroll
   for (int k = 0; k < AD; ++k) {
@@ -299,11 +242,10 @@ __device__ __forceinline__ void wave_gemm(f32x16v (&acc)[NT], const _Float16* Ah
       if constexpr (X3) aL[k][t] = *reinterpret_cast<const f16x8*>(Alo + aoff + t * FR * LDA + 16 * k);
     }
   }
-  // TCN_WPIPE (byte lo plane): the widened lo fragment of step s+1 computed during step s, so no VALU sits between a
-  // step's first and second MFMA (the second one's B operand)
-  constexpr bool WP = L8 && TCN_WPIPE;
+  // byte lo plane: the widened lo fragment of step s+1 computed during step s, so no VALU sits between a step's first
+  // and second MFMA (the second one's B operand)
   f16x8 blw;
-  if constexpr (WP) blw = lo8_widen<LQ>(rl[0], 0);
+  if constexpr (L8) blw = lo8_widen<LQ>(rl[0], 0);
   auto step = [&](int s, int i, bool pf) {
     const int cur = s % (AD + 1), nxt = (s + AD) % (AD + 1);
     if (s + AD < NS) {
@@ -321,8 +263,7 @@ __device__ __forceinline__ void wave_gemm(f32x16v (&acc)[NT], const _Float16* Ah
     } else if constexpr (X3) {
       const f16x8 bh = __builtin_bit_cast(f16x8, rh[i]);
       f16x8 bl;
-      if constexpr (WP) bl = blw;
-      else if constexpr (L8) bl = lo8_widen<LQ>(rl[i >> 1], i & 1);
+      if constexpr (L8) bl = blw;
       else bl = __builtin_bit_cast(f16x8, rl[i]);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -331,7 +272,7 @@ __device__ __forceinline__ void wave_gemm(f32x16v (&acc)[NT], const _Float16* Ah
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
       }
-      if constexpr (WP) {
+      if constexpr (L8) {
         if (s + 1 < NS) blw = lo8_widen<LQ>(rl[((i + 1) % RD) >> 1], (i + 1) & 1);
       }
     } else if constexpr (PRE == PREC_F16) {
@@ -367,7 +308,7 @@ __device__ __forceinline__ void wave_gemm(f32x16v (&acc)[NT], const _Float16* Ah
     for (int i = 0; i < RD; ++i) step(s0 + i, i, true);
   }
 #pragma unroll
-  for (int i = 0; i < RD; ++i) step(NS - RD + i, i, CONT);
+  for (int i = 0; i < RD; ++i) step(NS - RD + i, i, false);
   }
 }
 
@@ -446,8 +387,9 @@ __device__ __forceinline__ void block_sums(float (&v)[NV], float* lds, double* o
   // tid: the caller's recomputed thread id (tcn_common.h fresh_tid), so no value derived from threadIdx.x stays live
   // across the blocks (at 256 VGPRs hipcc spills such values to scratch and reloads them here behind vmcnt(0))
   const int w = tid >> 6;
-  if constexpr (TCN_BSRED && NV > 4) {
-    // wave totals by reduce-scatters of 16 values (rs16_wave: quad k of the wave holds value k), groups of 16
+  if constexpr (NV > 4) {
+    // (the moment record) wave totals by reduce-scatters of 16 values instead of NV DPP chains (rs16_wave: quad k of
+    // the wave holds value k), groups of 16
 #pragma unroll
     for (int g0 = 0; g0 < NV; g0 += 16) {
       float x[16];
@@ -506,7 +448,10 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   const int G = a.G;        // members (32-frame slices) per utterance
   const int GW = G / NSL;   // workgroups per group
-  if (TCN_PRIO && wave_s >= 4) __builtin_amdgcn_s_setprio(1);
+  // waves 4-7 at s_setprio 1 for the whole kernel (MI355X_MICROARCH.md "Static priority for the younger half"): they
+  // share each SIMD's MFMA pipe with waves 0-3 and, without it, finish every GEMM last (the barrier after the GEMM
+  // waits for them)
+  if (wave_s >= 4) __builtin_amdgcn_s_setprio(1);
   // block -> (group, workgroup g of the group): the groups of the first 8 * GW * floor(groups / 8) blocks each on one
   // XCD (blocks b, b + 8, ...: round-robin dispatch), the remaining groups (fewer than 8) on consecutive blocks, which
   // span XCDs (their hand-offs write through; speed only). Those take the highest group ids: with u = grp, grp +
@@ -555,11 +500,6 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
   // epoch 1: this workgroup's XCD id for each of its members (write-through), polled in the first utterance's prologue
   if (tid < NSL && grp < a.B)
     gput(slot(m0 + tid, 1), a.tag0 + 1, __builtin_amdgcn_s_getreg(6164) & 0xfu, false);  // hwreg(HW_REG_XCC_ID, 0, 4)
-  constexpr bool PP = TCN_PP && NSL == 1 && !F32;
-  unsigned ppn = 0;  // TCN_PP: blocks run by this workgroup (the LDS counters' target is 4 ppn)
-  if constexpr (PP) {
-    if (tid < 2) sm.ppc[tid] = 0u;  // (the prologue's barriers order this before every use)
-  }
   if (!a.tf_att) {  // no TF-attention: unit gates, so the gating multiply below is exact (two slices: not applied)
     if (tid < CH) sm.af[tid] = 1.f;
     if (tid < FW) sm.at[tid] = 1.f;
@@ -721,13 +661,14 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
       if (TP_ON && tid == 0 && u == grp && a.nblk > 5 && (bi == 0 || bi == 2))
         a.probe[((size_t)blockIdx.x * a.nblk + 4 + bi / 2) * 16 + 15] = __builtin_amdgcn_s_memtime();
       const __half* wb = a.wfrag + (size_t)bi * WL::BLOCK;
-      // TCN_FULLM: the frame masks of the row loops (rows r, r + 1 of a lane's tile rows: pair p = r / 2 of 8 NSL) only
-      // where a frame can be outside [0, T): none when every frame of the workgroup is inside (mpw = 0), the last two
-      // pairs when only its last 8 frames can be out (mpw = 2: the other pairs hold frames <= FW - 9; T mod 32 >= 24,
-      // e.g. T = 126, 188, 251), else all (a copy of each loop per case; the masks are 1 where skipped). The partial last
-      // member set every group's pace (the masked loops: cfg 2 138.1k vs 145.8k utt/s, profiles/r06mp/). The depthwise
-      // conv decides per wave (its 8 rows + halo).
-      const int mpw = !TCN_FULLM ? 8 * NSL : (t0 + FW <= T ? 0 : (t0 + FW - 8 <= T ? 2 : 8 * NSL));
+      // The frame masks of the row loops (rows r, r + 1 of a lane's tile rows: pair p = r / 2 of 8 NSL) only where a
+      // frame can be outside [0, T): none when every frame of the workgroup is inside (mpw = 0), the last two pairs
+      // when only its last 8 frames can be out (mpw = 2: the other pairs hold frames <= FW - 9; T mod 32 >= 24, e.g.
+      // T = 126, 188, 251), else all (a copy of each loop per case, taken by a uniform branch; the masks are 1 where
+      // skipped; bitwise neutral, and with it the two-slice kernels compile without spills). The partial last member
+      // set every group's pace (the masked loops: cfg 2 138.1k vs 145.8k utt/s, profiles/r06mp/). The depthwise conv
+      // decides per wave (its 8 rows + halo).
+      const int mpw = t0 + FW <= T ? 0 : (t0 + FW - 8 <= T ? 2 : 8 * NSL);
       auto by_mp = [&](auto&& f) {
         if (mpw == 0) f(std::integral_constant<int, 0>{});
         else if (mpw == 2) f(std::integral_constant<int, 2>{});
@@ -750,9 +691,9 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
       }
       // the epilogue's per-channel values straight into registers (no LDS round trip, no barrier)
       const float* pgl = a.prm + (size_t)bi * PB_SIZE;
-      // (TCN_A1V: a1 kept in a VGPR -- its readfirstlane was hoisted into the GEMM's first K step, where the wait for it
+      // (a1 kept in a VGPR, not readfirstlane'd: hipcc hoisted that into the GEMM's first K step, where the wait for it
       // (vmcnt) also waited for the parameter blob loads issued just before)
-      const float ws1 = pgl[PB_WS1 + m], b1 = pgl[PB_B1 + m], a1 = TCN_A1V ? pgl[PB_A1] : unif(pgl[PB_A1]);
+      const float ws1 = pgl[PB_WS1 + m], b1 = pgl[PB_B1 + m], a1 = pgl[PB_A1];
       const unsigned e1 = ++ep, tag1 = a.tag0 + e1;
       // ================= conv1d 256->256 (model/model.py:132) + PReLU =================
       f32x16v acc[NSL];
@@ -917,7 +858,7 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
           }
         };
         // (per wave: the thread's 8 rows fr0 .. fr0 + 7 and their halo, wave-uniform in both layouts)
-        const bool fullw = TCN_FULLDW && __builtin_amdgcn_readfirstlane((int)(TCN_FULLM && t0 + fr0 - 4 >= 0 && t0 + fr0 + FR / 4 + 4 <= T)) != 0;
+        const bool fullw = __builtin_amdgcn_readfirstlane((int)(t0 + fr0 - 4 >= 0 && t0 + fr0 + FR / 4 + 4 <= T)) != 0;
         if (fullw) rows_d(std::true_type{});
         else rows_d(std::false_type{});
       };
@@ -931,30 +872,7 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
       }
       // ---- P2 words: GN2 partial sums (awaited after the res_out main loop) ----
       const unsigned e2 = ++ep, tag2 = a.tag0 + e2;
-      // TCN_PP hand-over: wait until the 4 waves of K half hh have stored their d rows (LDS counter; s_sleep between reads)
-      auto pp_wait = [&](int hh) {
-        if constexpr (PP) {
-          while (__hip_atomic_load(&sm.ppc[hh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 4u * ppn)
-            __builtin_amdgcn_s_sleep(1);
-          asm volatile("" ::: "memory");
-        }
-      };
-      if constexpr (PP) {
-        // waves 4-7 (the s_setprio 1 waves: they win the VALU while both compute d) take K half 0 = input channels
-        // 0..127, waves 0-3 half 1; wave w's frames 8 (w & 3) .. + 7; vw = its wave in the plain mapping below
-        ++ppn;
-        const int hh = wave_s >= 4 ? 0 : 1, fq = wave_s & 3, vw = 2 * fq + hh;
-        f32x2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
-        dwconv(std::integral_constant<int, LDDE>{}, 2 * (64 * hh + lane), fq * (FR / 4), 0, 0, s0, s1);
-        // block_sums<2>'s wave totals (lane 63), at the plain mapping's wave index
-        float t0v = half_total(s0.x + s0.y), t1v = half_total(s1.x + s1.y);
-        t0v += dpp_f<0x143>(t0v);
-        t1v += dpp_f<0x143>(t1v);
-        if (lane == 63) { sm.pps[vw] = t0v; sm.pps[8 + vw] = t1v; }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's d rows and totals stored
-        if (lane == 0) __hip_atomic_fetch_add(&sm.ppc[hh], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      TPROBE(4);
-      } else if constexpr (NSL == 1) {
+      if constexpr (NSL == 1) {
         if (TCN_SUB == 1) TPROBE(13);
         f32x2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
         // thread = input channels c2, c2+1 (hidden 2c2..2c2+3) x frames fr0..fr0+7
@@ -970,25 +888,7 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
       for (int sl = 0; sl < NSL; ++sl)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[sl][r] = 0.f;
-      if constexpr (PP) {
-        if (wave_s >= 4) {  // K half 0 as soon as its d is complete, then half 1
-          pp_wait(0);
-          wave_gemm<NS2 / 2, LDDE, PRE, RD, LQ, 1, 0, true>(acc, sm.Ahi, sm.Alo, w2h, w2l, voff2, voff2l, rh, rl, lane);
-          pp_wait(1);
-          wave_gemm<NS2 / 2, LDDE, PRE, RD, LQ, 1, NS2 / 2>(acc, plane_at<PRE>(sm.Ahi, HID / 2), plane_at<PRE>(sm.Alo, HID / 2),
-                                                           w2h, w2l, voff2, voff2l, rh, rl, lane);
-        } else {  // all of d, then the whole K; threads 0, 1 publish the GN2 words (block_sums<2>'s order and bits)
-          pp_wait(1);
-          pp_wait(0);
-          if (tid < 2) {
-            double t = 0.0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) t += sm.pps[tid * 8 + i];
-            gputd(slot(g, e2) + GW_STAT + 2 * tid, tag2, t, l2);
-          }
-          wave_gemm<NS2, LDDE, PRE, RD, LQ>(acc, sm.Ahi, sm.Alo, w2h, w2l, voff2, voff2l, rh, rl, lane);
-        }
-      } else if constexpr (NSL == 1) {
+      if constexpr (NSL == 1) {
         wave_gemm<NS2, LDDE, PRE, RD, LQ>(acc, sm.Ahi, sm.Alo, w2h, w2l, voff2, voff2l, rh, rl, lane);
       } else {
         // two K halves of 256 hidden channels each (input channels 0..127, then 128..255 of the depthwise conv) through
@@ -1079,27 +979,15 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
               rsum = rs;
             });
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              if constexpr (TCN_RSRED) csr[r] = ws * acc[sl][r];
-              else
-              csr[r] = TCN_DIAG == 3 ? ws * acc[sl][r]  // (diagnostics: the 80 DPP adds per wave removed, wrong sums)
-                                     : half_total(ws * acc[sl][r]);  // ws-weighted sum over the wave's 32 channels (lanes 31 / 63)
-            }
-            if constexpr (TCN_RSRED) {
-              // ws-weighted sums over the wave's 32 channels of each frame by one reduce-scatter (lane L: row (L & 31) / 2
-              // of its half), stored by the even lanes
-              const float cv = rs16_half(csr, lane);
-              if ((lane & 1) == 0) sm.cs[trow(16 * sl + ((lane & 31) >> 1))][wave] = cv;
-              float ro = rsum;
-              swap32(rsum, ro);  // (ro: the other half's frames; a + b == b + a, the bits of the __shfl_xor form)
-              rsum += ro;
-            } else {
-            if ((lane & 31) == 31) {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) sm.cs[trow(16 * sl + r)][wave] = csr[r];
-            }
-            rsum += __shfl_xor(rsum, 32);
-            }
+            for (int r = 0; r < 16; ++r) csr[r] = ws * acc[sl][r];
+            // ws-weighted sums over the wave's 32 channels of each frame by one reduce-scatter over the 32-lane halves
+            // (lane L: row (L & 31) / 2 of its half), stored by the even lanes -- not 16 DPP chains of 5 (half_total), which
+            // a removal probe put at 2.9 % of k_tcn's cycles
+            const float cv = rs16_half(csr, lane);
+            if ((lane & 1) == 0) sm.cs[trow(16 * sl + ((lane & 31) >> 1))][wave] = cv;
+            float ro = rsum;
+            swap32(rsum, ro);  // (ro: the other half's frames; a + b == b + a, the bits of the __shfl_xor form)
+            rsum += ro;
             if (hl == 0) gputf(slot(m0 + sl, e3) + GW_ROW + m, tag3, rsum, tree ? sl2 : l2);
           }
         }
@@ -1423,8 +1311,7 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
                                                 : f32x2{t0 + tl < T ? 1.f : 0.f, t0 + tl + 1 < T ? 1.f : 0.f};
           const f32x2 ov = x * vm;
           o[r] = ov.x; o[r + 1] = ov.y;
-          if (TCN_XPK) split_store_rows_pk<PRE>(sm.Ahi, sm.Alo, tl * LDXE + m, LDXE, ov * sxn, (lane & 1) != 0);
-          else split_store_rows<PRE>(sm.Ahi, sm.Alo, tl * LDXE + m, LDXE, ov * sxn);
+          split_store_rows_pk<PRE>(sm.Ahi, sm.Alo, tl * LDXE + m, LDXE, ov * sxn, (lane & 1) != 0);
         }
         };
         by_mp(xup_rows);
