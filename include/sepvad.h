@@ -250,6 +250,41 @@ int32_t sepvad_stream_append(const float* src, int64_t src_ld, int64_t s0, int32
 int32_t sepvad_si_sdr(const float* P, int64_t p_ld, const float* Tg, int64_t t_ld, int64_t N, int32_t R,
                       const int32_t* pidx, const int32_t* tidx, int32_t zero_mean, float* out, void* stream);
 
+/* Replaces signal_noise_ratio (model/metric.py:104-143; PIT over it: metric.py:255-256 pit_snr) with the argument
+ * list of the SI-SDR entry above: out[r] = 10 log10((<t,t> + eps) / (<t - p, t - p> + eps)) in dB, p = P[pidx[r]],
+ * t = Tg[tidx[r]], optional zero mean, eps = float32 epsilon. The same five double moments, fixed order. */
+int32_t sepvad_snr(const float* P, int64_t p_ld, const float* Tg, int64_t t_ld, int64_t N, int32_t R,
+                   const int32_t* pidx, const int32_t* tidx, int32_t zero_mean, float* out, void* stream);
+
+/* ---- STOI (model/stoi_metric.py:207-301 stoi, extended=False; model/metric.py:207-223 Stoi) ----------
+ * HOST function, no GPU needed: the design the device path uses for signals sampled at fs_sig (8000, 10000 or
+ * 16000 Hz). taps (capacity `cap` floats) receive the resampling window h / sum(h) of _resample_window_oct and
+ * resample_oct (stoi_metric.py:11-52), computed in double and rounded to float: 581 taps at 16 kHz (5/8), 365 at
+ * 8 kHz (5/4), none at 10 kHz. info[SEPVAD_STOI_INFO_LEN] receives {up, down, ntaps, 15} followed by the 15
+ * third-octave bands of thirdoct / OBM (stoi_metric.py:55-85,201) as {first bin, one past the last bin} pairs of the
+ * 512-point spectrum at 10 kHz. taps NULL = size query. SEPVAD_E_ARG on a short buffer or another rate. */
+#define SEPVAD_STOI_INFO_LEN 34
+int32_t sepvad_stoi_filter(int32_t fs_sig, float* taps, int32_t cap, int32_t* info);
+
+/* HOST function: bytes of device scratch the STOI entry below needs for R pairs of N samples at fs_sig (the
+ * resampled signals, frame energies, kept-frame lists and band magnitudes, sized for every frame kept). Negative
+ * status if the rate is unsupported, R is outside 1..65535 or N gives no frame (256 samples or fewer at 10 kHz). */
+int64_t sepvad_stoi_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig);
+
+/* Replaces stoi(x, y, fs_sig) (model/stoi_metric.py:207-301, extended=False) for R signal pairs in one call:
+ * out[r] = STOI of clean X[xidx[r]] against estimate Y[yidx[r]] (rows of N samples with row strides x_ld / y_ld,
+ * index arrays nullable = identity, so PIT pairings need no gather). Resampling to 10 kHz, silent-frame removal
+ * (40 dB below the loudest clean frame), 512-point STFT, 15 third-octave bands and the clipped, normalised
+ * correlation over windows of 30 frames all run on the device without a host synchronisation; the arithmetic is
+ * double apart from the float store of the resampled signals. frames (nullable) receives M, the number of spectra
+ * left after silence removal; out[r] is exactly 1e-5 when M < 30 (stoi_metric.py:251-256, without its warning).
+ * scratch: 256-byte aligned device memory of scratch_bytes >= the size query above. Fixed-order reductions per
+ * pair: bitwise reproducible, independent of R and of the other pairs. Device pointers, stream-ordered (the first
+ * call per device and rate uploads the design tables synchronously). */
+int32_t sepvad_stoi(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, int64_t N, int32_t R,
+                    const int32_t* xidx, const int32_t* yidx, int32_t fs_sig, void* scratch, int64_t scratch_bytes,
+                    double* out, int32_t* frames, void* stream);
+
 /* Replaces Accuracy_Vad()(preds, targets, _) (model/metric.py:163-177): labels = preds > 0.5 (NaN kept),
  * written back into preds when in_place (the reference masks its argument in place); out[0] = fraction of
  * labels equal to targets over [B, S, T], out[1 + s] = the same for speaker s (S <= 8). Device pointers,

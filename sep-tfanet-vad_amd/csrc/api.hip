@@ -35,6 +35,7 @@
 
 #include "../../include/sepvad.h"
 #include "sepvad_internal.h"
+#include "stoi_design.h"
 
 using namespace sepvad;
 
@@ -1989,6 +1990,64 @@ int32_t sepvad_si_sdr(const float* P, int64_t p_ld, const float* Tg, int64_t t_l
   a.P = P; a.p_ld = p_ld; a.Tg = Tg; a.t_ld = t_ld; a.N = N; a.R = R; a.pidx = pidx; a.tidx = tidx;
   a.zero_mean = zero_mean; a.out = out;
   HIPCHK(launch_si_sdr(a, (hipStream_t)stream));
+  return SEPVAD_OK;
+}
+
+int32_t sepvad_snr(const float* P, int64_t p_ld, const float* Tg, int64_t t_ld, int64_t N, int32_t R,
+                   const int32_t* pidx, const int32_t* tidx, int32_t zero_mean, float* out, void* stream) {
+  if (!P || !Tg || !out || N < 1 || R < 1 || p_ld < N || t_ld < N) return fail(SEPVAD_E_ARG, "sepvad_snr: bad arguments");
+  SiSdrArgs a{};
+  a.P = P; a.p_ld = p_ld; a.Tg = Tg; a.t_ld = t_ld; a.N = N; a.R = R; a.pidx = pidx; a.tidx = tidx;
+  a.zero_mean = zero_mean; a.out = out;
+  HIPCHK(launch_snr(a, (hipStream_t)stream));
+  return SEPVAD_OK;
+}
+
+int32_t sepvad_stoi_filter(int32_t fs_sig, float* taps, int32_t cap, int32_t* info) {
+  StoiDesign d;
+  if (!info || !stoi_design(fs_sig, d)) return fail(SEPVAD_E_ARG, "sepvad_stoi_filter: fs_sig must be 8000, 10000 or 16000");
+  const int ntaps = (int)d.w.size();
+  info[0] = d.up; info[1] = d.down; info[2] = ntaps; info[3] = STOI_BANDS;
+  for (int b = 0; b < STOI_BANDS; ++b) {
+    info[4 + 2 * b] = d.lo[b];
+    info[5 + 2 * b] = d.hi[b];
+  }
+  if (!taps) return SEPVAD_OK;  // size query
+  if (cap < ntaps) return fail(SEPVAD_E_ARG, "sepvad_stoi_filter: taps capacity too small");
+  for (int i = 0; i < ntaps; ++i) taps[i] = (float)d.w[i];
+  return SEPVAD_OK;
+}
+
+// (R, N, fs_sig) that sepvad_stoi accepts: at least one frame after resampling, grid and index ranges
+static bool stoi_shape_ok(int32_t R, int64_t N, int up, int down) {
+  if (R < 1 || R > 65535 || N < 1 || N > (1LL << 31)) return false;
+  const long long nF = stoi_num_frames(stoi_resampled_len(N, up, down));
+  return nF >= 1 && (long long)R * 2 * STOI_BANDS * nF < (1LL << 40);
+}
+
+int64_t sepvad_stoi_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig) {
+  StoiDesign d;
+  if (!stoi_design(fs_sig, d)) return fail(SEPVAD_E_ARG, "sepvad_stoi_scratch_bytes: fs_sig must be 8000, 10000 or 16000");
+  if (!stoi_shape_ok(R, N, d.up, d.down))
+    return fail(SEPVAD_E_ARG, "sepvad_stoi_scratch_bytes: need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
+  return stoi_scratch_layout(R, N, d.up, d.down, nullptr, nullptr);
+}
+
+int32_t sepvad_stoi(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, int64_t N, int32_t R,
+                    const int32_t* xidx, const int32_t* yidx, int32_t fs_sig, void* scratch, int64_t scratch_bytes,
+                    double* out, int32_t* frames, void* stream) {
+  if (!X || !Y || !out || !scratch || N < 1 || x_ld < N || y_ld < N) return fail(SEPVAD_E_ARG, "sepvad_stoi: bad arguments");
+  if (!stoi_rate_supported(fs_sig)) return fail(SEPVAD_E_ARG, "sepvad_stoi: fs_sig must be 8000, 10000 or 16000");
+  StoiArgs a{};
+  HIPCHK(stoi_tables(fs_sig, a));
+  if (!stoi_shape_ok(R, N, a.up, a.down))
+    return fail(SEPVAD_E_ARG, "sepvad_stoi: need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
+  if (scratch_bytes < stoi_scratch_layout(R, N, a.up, a.down, &a, (char*)scratch))
+    return fail(SEPVAD_E_ARG, "sepvad_stoi: scratch too small (sepvad_stoi_scratch_bytes)");
+  if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail(SEPVAD_E_ARG, "sepvad_stoi: scratch must be 256-byte aligned");
+  a.X = X; a.x_ld = x_ld; a.Y = Y; a.y_ld = y_ld; a.xidx = xidx; a.yidx = yidx; a.N = N; a.R = R;
+  a.out = out; a.frames = frames;
+  HIPCHK(launch_stoi(a, (hipStream_t)stream));
   return SEPVAD_OK;
 }
 

@@ -13,7 +13,8 @@ namespace sepvad {
 
 constexpr int SD_THREADS = 256;
 
-__global__ __launch_bounds__(SD_THREADS) void k_si_sdr(SiSdrArgs a) {
+// The five double moments of pair r; true on thread 0 only, which then holds them in m.
+__device__ __forceinline__ bool pair_moments(const SiSdrArgs& a, double (&m)[5]) {
   __shared__ double red[5 * 16];
   const int r = blockIdx.x;
   const long long pr = a.pidx ? a.pidx[r] : r, tr = a.tidx ? a.tidx[r] : r;
@@ -49,14 +50,21 @@ __global__ __launch_bounds__(SD_THREADS) void k_si_sdr(SiSdrArgs a) {
     if (l == 0) red[k * 16 + w] = v;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double m[5];
+  if (threadIdx.x != 0) return false;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      double v = 0.0;
-      for (int i = 0; i < SD_THREADS / 64; ++i) v += red[k * 16 + i];
-      m[k] = v;
-    }
+  for (int k = 0; k < 5; ++k) {
+    double v = 0.0;
+    for (int i = 0; i < SD_THREADS / 64; ++i) v += red[k * 16 + i];
+    m[k] = v;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(SD_THREADS) void k_si_sdr(SiSdrArgs a) {
+  double m[5];
+  if (pair_moments(a, m)) {
+    const int r = blockIdx.x;
+    const long long N = a.N;
     const double eps = 1.1920928955078125e-07;  // torch.finfo(torch.float32).eps
     const double Nd = (double)N;
     double pt = m[4], tt = m[3], pp = m[2];
@@ -71,6 +79,26 @@ __global__ __launch_bounds__(SD_THREADS) void k_si_sdr(SiSdrArgs a) {
     double noise = sig - 2.0 * alpha * pt + pp;
     if (noise < 0.0) noise = 0.0;
     a.out[r] = (float)(10.0 * log10((sig + eps) / (noise + eps)));
+  }
+}
+
+// Signal-to-noise ratio (reference model/metric.py:104-143 signal_noise_ratio): optional zero mean, noise = t - p,
+//   snr = 10 log10((<t,t> + eps) / (<noise,noise> + eps)),  <noise,noise> = <t',t'> - 2 <p',t'> + <p',p'>.
+__global__ __launch_bounds__(SD_THREADS) void k_snr(SiSdrArgs a) {
+  double m[5];
+  if (pair_moments(a, m)) {
+    const double eps = 1.1920928955078125e-07;  // torch.finfo(torch.float32).eps
+    const double Nd = (double)a.N;
+    double pt = m[4], tt = m[3], pp = m[2];
+    if (a.zero_mean) {
+      const double mp = m[0] / Nd, mt = m[1] / Nd;
+      pt -= Nd * mp * mt;
+      tt -= Nd * mt * mt;
+      pp -= Nd * mp * mp;
+    }
+    double noise = tt - 2.0 * pt + pp;
+    if (noise < 0.0) noise = 0.0;
+    a.out[blockIdx.x] = (float)(10.0 * log10((tt + eps) / (noise + eps)));
   }
 }
 
@@ -122,6 +150,12 @@ hipError_t launch_vad_acc(const VadAccArgs& a, hipStream_t s) {
 hipError_t launch_si_sdr(const SiSdrArgs& a, hipStream_t s) {
   if (a.R < 1 || a.N < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_si_sdr, dim3(a.R), dim3(SD_THREADS), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_snr(const SiSdrArgs& a, hipStream_t s) {
+  if (a.R < 1 || a.N < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_snr, dim3(a.R), dim3(SD_THREADS), 0, s, a);
   return hipGetLastError();
 }
 

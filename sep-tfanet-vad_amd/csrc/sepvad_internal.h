@@ -270,6 +270,32 @@ struct SiSdrArgs {
   float* out;
 };
 hipError_t launch_si_sdr(const SiSdrArgs& a, hipStream_t s);
+hipError_t launch_snr(const SiSdrArgs& a, hipStream_t s);  // signal_noise_ratio: the same moments, another closed form
+
+// STOI (stoi.hip; host design in stoi_design.h)
+struct StoiArgs {
+  const float* X; long long x_ld;   // clean rows
+  const float* Y; long long y_ld;   // estimate rows
+  const int* xidx; const int* yidx; // nullable row indices per pair
+  long long N; int R;
+  int up, down, half, Q;            // resampler (up == down: identity, the inputs are read in place)
+  long long L;                      // samples per signal at 10 kHz
+  int nF;                           // frames before silence removal (worst case of the kept count)
+  const double* tp;                 // [up][Q] polyphase taps (device)
+  const double* win;                // [256] analysis window (device)
+  const double* tw;                 // [256] complex twiddles (device)
+  int lo[15], hi[15];               // band b: bins lo .. hi - 1
+  float* sig;                       // [R][2][Ls] resampled signals (scratch; unused for identity)
+  long long Ls;
+  double* energy;                   // [R][nF] clean frame energies
+  int* kept;                        // [R][nF] kept frame k -> frame index
+  int* nkept;                       // [R]
+  double* tob;                      // [R][2][15][nF] third-octave magnitudes of spectrum m
+  double* out; int* frames;         // [R]; frames nullable
+};
+long long stoi_scratch_layout(int R, long long N, int up, int down, StoiArgs* a, char* base);  // bytes
+hipError_t stoi_tables(int fs_sig, StoiArgs& a);  // device-resident taps / window / twiddles of the current device
+hipError_t launch_stoi(const StoiArgs& a, hipStream_t s);
 constexpr int VACC_MAX_S = 8;
 struct VadAccArgs {
   float* preds; const float* targets;   // [B][S][T]

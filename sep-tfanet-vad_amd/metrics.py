@@ -12,9 +12,14 @@
   SI-SDR of the mixture against each target.
 * ``Accuracy_Vad`` (``model/metric.py:163-177``): thresholded (``> 0.5``) VAD label accuracy, overall and per
   speaker; like the reference it thresholds ``preds`` in place (``k_vad_acc``, exact integer counts).
+* ``signal_noise_ratio`` (``model/metric.py:104-143``) and ``pit_snr`` (``:255-256``): the SNR of the same row
+  pairs (``k_snr``, the moments of ``k_si_sdr`` with another closed form) and the PIT reduction over it.
+* ``stoi`` (``model/stoi_metric.py:207-301``, classic STOI; ``extended=True`` draws ``np.random`` noise and is
+  refused), the ``Stoi`` module and ``stoi_met`` (``model/metric.py:207-223,276-277``): every pair of a batch in one
+  call of ``sepvad_stoi`` (csrc/stoi.hip), float64 results on the device, no host round trip.
 
-All inputs are ROCm tensors; the arithmetic runs in ``k_si_sdr`` (csrc/metrics.hip) through the C ABI
-``sepvad_si_sdr``. There is no CPU fallback.
+All inputs are ROCm tensors; the arithmetic runs in ``k_si_sdr`` / ``k_snr`` (csrc/metrics.hip) and the ``k_stoi_*``
+kernels (csrc/stoi.hip) through the C ABI. There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -37,18 +42,23 @@ def _rows(x: torch.Tensor) -> torch.Tensor:
     return x.to(torch.float32).reshape(-1, x.shape[-1]).contiguous()
 
 
-def _si_sdr_pairs(P, Tg, pidx=None, tidx=None, zero_mean=True):
-    """SI-SDR of rows P[pidx[r]] vs Tg[tidx[r]] (2-D contiguous float32 device tensors)."""
+def _si_sdr_pairs(P, Tg, pidx=None, tidx=None, zero_mean=True, entry="sepvad_si_sdr"):
+    """SI-SDR (or, with entry="sepvad_snr", SNR) of rows P[pidx[r]] vs Tg[tidx[r]] (2-D contiguous float32
+    device tensors)."""
     lib = _native.load_library()
     R = len(pidx) if pidx is not None else P.shape[0]
     out = torch.empty(R, device=P.device, dtype=torch.float32)
     pi = torch.as_tensor(pidx, dtype=torch.int32, device=P.device) if pidx is not None else None
     ti = torch.as_tensor(tidx, dtype=torch.int32, device=P.device) if tidx is not None else None
     stream = torch.cuda.current_stream(P.device).cuda_stream
-    rc = lib.sepvad_si_sdr(_native._ptr(P), P.shape[1], _native._ptr(Tg), Tg.shape[1], P.shape[1], R,
-                           _native._ptr(pi), _native._ptr(ti), int(bool(zero_mean)), _native._ptr(out), stream)
-    _native._check(rc, "sepvad_si_sdr")
+    rc = getattr(lib, entry)(_native._ptr(P), P.shape[1], _native._ptr(Tg), Tg.shape[1], P.shape[1], R,
+                             _native._ptr(pi), _native._ptr(ti), int(bool(zero_mean)), _native._ptr(out), stream)
+    _native._check(rc, entry)
     return out
+
+
+def _snr_pairs(P, Tg, pidx=None, tidx=None, zero_mean=True):
+    return _si_sdr_pairs(P, Tg, pidx, tidx, zero_mean, entry="sepvad_snr")
 
 
 def scale_invariant_signal_distortion_ratio(preds: torch.Tensor, target: torch.Tensor, zero_mean: bool = True):
@@ -66,12 +76,20 @@ def calc_sisdr_loss(preds, target, zero_mean: bool = True):
     return -calc_sisdr(preds, target, zero_mean)
 
 
-def permutation_invariant_si_sdr(preds: torch.Tensor, target: torch.Tensor, zero_mean: bool = True):
+def signal_noise_ratio(preds: torch.Tensor, target: torch.Tensor, zero_mean: bool = True):
+    """model/metric.py:104-143 (note its default: zero_mean=True, unlike torchmetrics)."""
+    _check_same_shape(preds, target)
+    P, Tg = _rows(preds), _rows(target)
+    return _snr_pairs(P, Tg, zero_mean=zero_mean).reshape(preds.shape[:-1])
+
+
+def permutation_invariant_si_sdr(preds: torch.Tensor, target: torch.Tensor, zero_mean: bool = True,
+                                 pairwise=_si_sdr_pairs):
     """Per-utterance best permutation for [B, S, time] inputs.
 
     Returns (best_metric [B], best_perm [B, S] int64): metric matrix m[b, t, p] = SI-SDR(preds[b, p],
-    target[b, t]); perm value = mean_t m[b, t, perm[t]]; the first maximum over permutations in
-    itertools order (torchmetrics' exhaustive search)."""
+    target[b, t]) (or another `pairwise` row-pair metric); perm value = mean_t m[b, t, perm[t]]; the first
+    maximum over permutations in itertools order (torchmetrics' exhaustive search)."""
     _check_same_shape(preds, target)
     B, S, N = preds.shape
     P, Tg = _rows(preds), _rows(target)
@@ -81,7 +99,7 @@ def permutation_invariant_si_sdr(preds: torch.Tensor, target: torch.Tensor, zero
             for p in range(S):
                 pidx.append(b * S + p)
                 tidx.append(b * S + t)
-    mtx = _si_sdr_pairs(P, Tg, pidx, tidx, zero_mean).reshape(B, S, S)
+    mtx = pairwise(P, Tg, pidx, tidx, zero_mean).reshape(B, S, S)
     perms = torch.tensor(list(itertools.permutations(range(S))), device=preds.device)  # [P!, S]
     vals = mtx[:, torch.arange(S, device=preds.device), perms].mean(dim=-1)           # [B, P!]
     best, idx = vals.max(dim=-1)
@@ -92,6 +110,106 @@ def pit_si_sdr(preds: torch.Tensor, target: torch.Tensor):
     """model/metric.py:258: mean over the batch of the best-permutation SI-SDR."""
     best, _ = permutation_invariant_si_sdr(preds, target, zero_mean=True)
     return best.mean()
+
+
+def permutation_invariant_snr(preds: torch.Tensor, target: torch.Tensor, zero_mean: bool = True):
+    """permutation_invariant_si_sdr over signal_noise_ratio."""
+    return permutation_invariant_si_sdr(preds, target, zero_mean, pairwise=_snr_pairs)
+
+
+def pit_snr(preds: torch.Tensor, target: torch.Tensor):
+    """model/metric.py:255-256: mean over the batch of the best-permutation SNR (zero_mean=True)."""
+    best, _ = permutation_invariant_snr(preds, target, zero_mean=True)
+    return best.mean()
+
+
+# test.py:149-151 calls `metric.to(device)` and reads `metric.__name__` on every entry of config["metrics"]["separation"]
+# (the reference's are torchmetrics objects); the functions here hold no state, so .to returns them unchanged
+pit_snr.to = lambda *args, **kwargs: pit_snr
+pit_si_sdr.to = lambda *args, **kwargs: pit_si_sdr
+
+
+_stoi_scratch = {}  # (device, stream) -> uint8 scratch, most recently used last (as pit._scratch_for)
+
+
+def _stoi_scratch_for(device, nbytes):
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    buf = _stoi_scratch.pop(key, None)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        while len(_stoi_scratch) >= 32:
+            _stoi_scratch.pop(next(iter(_stoi_scratch)))
+    _stoi_scratch[key] = buf
+    return buf
+
+
+def stoi_filter(fs_sig: int):
+    """Host design of the STOI front end (sepvad_stoi_filter, no GPU): (taps float32 [ntaps] = h / sum(h) of
+    stoi_metric.py:11-52, (up, down), bands int32 [15, 2] = first bin / one past the last bin of OBM, :201)."""
+    import ctypes
+    import numpy as np
+    lib = _native.load_library()
+    info = (ctypes.c_int32 * 34)()
+    _native._check(lib.sepvad_stoi_filter(int(fs_sig), None, 0, info), "sepvad_stoi_filter")
+    taps = np.zeros(info[2], np.float32)
+    _native._check(lib.sepvad_stoi_filter(int(fs_sig), taps.ctypes.data_as(ctypes.c_void_p), taps.size, info),
+                   "sepvad_stoi_filter")
+    return taps, (info[0], info[1]), np.array(info[4:34], np.int32).reshape(15, 2)
+
+
+def stoi_pairs(X, Y, fs_sig, xidx=None, yidx=None):
+    """STOI of clean rows X[xidx[r]] vs estimate rows Y[yidx[r]] (2-D contiguous float32 device tensors of one
+    length). Returns (d [R] float64, M [R] int32: spectra left after silence removal; d is exactly 1e-5 where
+    M < 30, as the reference returns with a warning)."""
+    lib = _native.load_library()
+    if X.shape[1] != Y.shape[1]:
+        raise RuntimeError(f"x and y should have the same length, found {X.shape[1]} and {Y.shape[1]}")
+    N = X.shape[1]
+    R = len(xidx) if xidx is not None else X.shape[0]
+    dev = X.device
+    nbytes = lib.sepvad_stoi_scratch_bytes(R, N, int(fs_sig))
+    if nbytes < 0:
+        _native._check(int(nbytes), "sepvad_stoi_scratch_bytes")
+    scratch = _stoi_scratch_for(dev, nbytes)
+    out = torch.empty(R, device=dev, dtype=torch.float64)
+    frames = torch.empty(R, device=dev, dtype=torch.int32)
+    xi = torch.as_tensor(xidx, dtype=torch.int32, device=dev) if xidx is not None else None
+    yi = torch.as_tensor(yidx, dtype=torch.int32, device=dev) if yidx is not None else None
+    rc = lib.sepvad_stoi(_native._ptr(X), X.shape[1], _native._ptr(Y), Y.shape[1], N, R, _native._ptr(xi),
+                         _native._ptr(yi), int(fs_sig), _native._ptr(scratch), scratch.numel(), _native._ptr(out),
+                         _native._ptr(frames), torch.cuda.current_stream(dev).cuda_stream)
+    _native._check(rc, "sepvad_stoi")
+    return out, frames
+
+
+def stoi(x: torch.Tensor, y: torch.Tensor, fs_sig: int, extended: bool = False):
+    """model/stoi_metric.py:207-301 with the reference's argument order (x clean, y processed): [..., time] ROCm
+    tensors -> [...] float64 on the device."""
+    if extended:
+        raise NotImplementedError("extended STOI adds np.random noise in the reference (stoi_metric.py:177-193) "
+                                  "and is not provided")
+    if x.shape != y.shape:
+        raise RuntimeError(f"x and y should have the same length, found {tuple(x.shape)} and {tuple(y.shape)}")
+    X, Y = _rows(x), _rows(y)
+    return stoi_pairs(X, Y, fs_sig)[0].reshape(x.shape[:-1])
+
+
+class Stoi(torch.nn.Module):
+    """model/metric.py:207-223: preds, targets [B, num_spk, time] -> mean STOI over [B, num_spk] (0-dim float64
+    device tensor). The reference hard-codes 16 kHz; fs_sig overrides it. batch_indices_separation is unused
+    there as well."""
+
+    def __init__(self, fs_sig: int = 16000):
+        super().__init__()
+        self.fs_sig = fs_sig
+
+    def forward(self, preds, targets, batch_indices_separation=None):
+        _check_same_shape(preds, targets)
+        return stoi(targets, preds, self.fs_sig).mean()
+
+
+stoi_met = Stoi()
+stoi_met.__name__ = "stoi_metric"
 
 
 class SI_SDRi(torch.nn.Module):
@@ -126,3 +244,7 @@ class Accuracy_Vad(torch.nn.Module):
         if work is not preds:
             preds.copy_(work)
         return out[0], out[1], out[2]
+
+
+vad_accuracy = Accuracy_Vad()  # model/metric.py:270-271
+vad_accuracy.__name__ = "vad_accuracy"

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "sepvad_stft", "sepvad_istft",
     "sepvad_pit_l1", "sepvad_stream_append",
     "sepvad_resample_filter", "sepvad_resample", "sepvad_normalize", "sepvad_si_sdr", "sepvad_vad_accuracy",
+    "sepvad_snr", "sepvad_stoi_filter", "sepvad_stoi_scratch_bytes", "sepvad_stoi",
     "sepvad_rir_generate",
     "sepvad_set_timing", "sepvad_timing", "sepvad_destroy", "sepvad_last_error", "sepvad_abi_version",
     "sepvad_build_id",
@@ -147,6 +148,14 @@ def load_library(path: str = LIB_PATH):
     lib.sepvad_normalize.argtypes = [P, i64, P, P, P]
     lib.sepvad_si_sdr.restype = i32
     lib.sepvad_si_sdr.argtypes = [P, i64, P, i64, i64, i32, P, P, i32, P, P]
+    lib.sepvad_snr.restype = i32
+    lib.sepvad_snr.argtypes = [P, i64, P, i64, i64, i32, P, P, i32, P, P]
+    lib.sepvad_stoi_filter.restype = i32
+    lib.sepvad_stoi_filter.argtypes = [i32, P, i32, P]
+    lib.sepvad_stoi_scratch_bytes.restype = i64
+    lib.sepvad_stoi_scratch_bytes.argtypes = [i32, i64, i32]
+    lib.sepvad_stoi.restype = i32
+    lib.sepvad_stoi.argtypes = [P, i64, P, i64, i64, i32, P, P, i32, P, i64, P, P, P]
     lib.sepvad_vad_accuracy.restype = i32
     lib.sepvad_vad_accuracy.argtypes = [P, P, i32, i32, i32, i32, P, P]
     dptr = ctypes.POINTER(ctypes.c_double)
