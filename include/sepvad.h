@@ -249,6 +249,44 @@ int32_t sepvad_pit_l1_choose(const double* sums, double count, int32_t B, int64_
 int32_t sepvad_stream_append(const float* src, int64_t src_ld, int64_t s0, int32_t B, int64_t H,
                              const int64_t* perm, float* dst, int64_t dst_ld, int64_t d0, void* stream);
 
+/* ---- live sessions: the same wrapper fed a chunk at a time ------------------------------------
+ * Stateless like the entries above: the caller owns the rings and the counters (live.py does).
+ *
+ * Extends get_truncated_signal (model/online_class_unknown_targets.py:39-41) to input that arrives in
+ * chunks. ring is [rows][2R] f32, a mirrored ring: sample j of chunk row r ([rows][chunk_ld], n samples) is
+ * stored at ring[r][(pos + j) % R] and again at that index + R, so after any push every span of up to R most
+ * recent samples is contiguous in memory and a window (or several, hop apart) goes to sepvad_forward_strided /
+ * sepvad_forward_windows with a row stride of 2R and no gather copy. The caller advances pos by n modulo R.
+ * SEPVAD_E_ARG (nothing launched) for a null pointer, n < 1, n > R, pos outside [0, R) or chunk_ld < n. */
+int32_t sepvad_ring_push(const float* chunk, int64_t chunk_ld, int32_t rows, int64_t n, float* ring, int64_t R,
+                         int64_t pos, void* stream);
+
+/* The PIT-L1 of sepvad_pit_l1 (model/pit_wrapper.py:149-177,261-312) applied to each row on its own: what the
+ * window loop (model/online_class_unknown_targets.py:72-97) computes for a batch of one stream, for B
+ * independent streams in one call. Row b's perm_out[b][2], loss_out[b] and pw_out[b][4] (each nullable) have
+ * the bits of sepvad_pit_l1 called on that row alone with B = 1: the same blocks per row, accumulation and
+ * reduction order. Ties keep the identity permutation. scratch: device buffer of scratch_bytes >=
+ * sepvad_pit_l1_rows_scratch_bytes (host query; negative for B < 1, B > 65535 or L < 1). */
+int64_t sepvad_pit_l1_rows_scratch_bytes(int32_t B, int64_t L);
+int32_t sepvad_pit_l1_rows(const float* est, int64_t est_ld, const float* ref, int64_t ref_ld, int32_t B, int64_t L,
+                           void* scratch, int64_t scratch_bytes, int64_t* perm_out, float* loss_out, float* pw_out,
+                           void* stream);
+
+/* One emitted window: reorder_source_mse (model/combined_loss.py:63-78) + update_online_signal
+ * (model/online_class_unknown_targets.py:28-37) on the window's last hop, kept as a chunk and a tail instead of
+ * a growing signal. win is one window's separation [B][2][win_ld] of N samples. For row b, output speaker i and
+ * p = perm[b][i] (perm NULL = identity), n < H:
+ *   out[b][i][d0 + n] = win[b][p][N - H + n]                       (out [B][2][out_ld], the caller's chunk)
+ *   tail[b][i][(tpos + n) % Rt] and the same index + Rt            (mirrored ring [B][2][2Rt]: the stitched
+ *                        signal's last Rt samples stay contiguous for the next window's PIT, :87-91)
+ *   vad_out[b][i][v0 + j] = vad[b][p][T - nf + j], j < nf           (vad nullable: [B][2][T] of the window)
+ * SEPVAD_E_ARG (nothing launched) for a null pointer, H > Rt, H > N, nf > T, tpos outside [0, Rt) or offsets
+ * that leave their rows. */
+int32_t sepvad_live_stitch(const float* win, int64_t win_ld, int64_t N, int32_t B, int64_t H, const int64_t* perm,
+                           float* out, int64_t out_ld, int64_t d0, float* tail, int64_t Rt, int64_t tpos,
+                           const float* vad, int32_t T, int32_t nf, float* vad_out, int64_t vad_ld, int64_t v0,
+                           void* stream);
+
 /* ---- quality metrics (model/combined_loss.py:16-56 calc_sisdr == model/metric.py:61-101
  * scale_invariant_signal_distortion_ratio; PIT over it: metric.py:258 pit_si_sdr) --------------------
  * out[r] = SI-SDR(P[pidx[r]], Tg[tidx[r]]) in dB for r < R: rows of N samples with row strides p_ld / t_ld,

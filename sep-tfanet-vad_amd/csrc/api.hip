@@ -1944,6 +1944,66 @@ int32_t sepvad_stream_append(const float* src, int64_t src_ld, int64_t s0, int32
   return SEPVAD_OK;
 }
 
+int32_t sepvad_ring_push(const float* chunk, int64_t chunk_ld, int32_t rows, int64_t n, float* ring, int64_t R,
+                         int64_t pos, void* stream) {
+  if (!chunk || !ring) return fail(SEPVAD_E_ARG, "sepvad_ring_push: null pointer");
+  if (rows < 1 || R < 1) return fail(SEPVAD_E_ARG, "sepvad_ring_push: rows and R must be >= 1");
+  if (n < 1 || n > R) return fail(SEPVAD_E_ARG, "sepvad_ring_push: need 1 <= n <= R");
+  if (pos < 0 || pos >= R) return fail(SEPVAD_E_ARG, "sepvad_ring_push: pos must be in [0, R)");
+  if (chunk_ld < n) return fail(SEPVAD_E_ARG, "sepvad_ring_push: chunk_ld must be >= n");
+  RingPushArgs a{};
+  a.rows = rows; a.n = n; a.R = R; a.pos = pos; a.chunk = chunk; a.chunk_ld = chunk_ld; a.ring = ring;
+  HIPCHK(launch_ring_push(a, (hipStream_t)stream));
+  return SEPVAD_OK;
+}
+
+int64_t sepvad_pit_l1_rows_scratch_bytes(int32_t B, int64_t L) {
+  if (B < 1 || B > 65535 || L < 1) return fail(SEPVAD_E_ARG, "sepvad_pit_l1_rows_scratch_bytes: need 1 <= B <= 65535, L >= 1");
+  return (int64_t)B * pit_row_blocks(L) * 4 * (int64_t)sizeof(double);
+}
+
+int32_t sepvad_pit_l1_rows(const float* est, int64_t est_ld, const float* ref, int64_t ref_ld, int32_t B, int64_t L,
+                           void* scratch, int64_t scratch_bytes, int64_t* perm_out, float* loss_out, float* pw_out,
+                           void* stream) {
+  if (!est || !ref || !scratch) return fail(SEPVAD_E_ARG, "sepvad_pit_l1_rows: null pointer");
+  if (B < 1 || B > 65535 || L < 1 || est_ld < L || ref_ld < L)
+    return fail(SEPVAD_E_ARG, "sepvad_pit_l1_rows: need 1 <= B <= 65535, L >= 1 and row strides >= L");
+  if (scratch_bytes < (int64_t)B * pit_row_blocks(L) * 4 * (int64_t)sizeof(double))
+    return fail(SEPVAD_E_ARG, "sepvad_pit_l1_rows: scratch too small (sepvad_pit_l1_rows_scratch_bytes)");
+  PitArgs a{};
+  a.B = B; a.L = L; a.est = est; a.est_ld = est_ld; a.ref = ref; a.ref_ld = ref_ld;
+  a.nblk = pit_row_blocks(L);
+  a.partial = (double*)scratch;
+  a.perm_out = (long long*)perm_out; a.loss_out = loss_out; a.pw_out = pw_out;
+  HIPCHK(launch_pit_l1_rows(a, (hipStream_t)stream));
+  return SEPVAD_OK;
+}
+
+int32_t sepvad_live_stitch(const float* win, int64_t win_ld, int64_t N, int32_t B, int64_t H, const int64_t* perm,
+                           float* out, int64_t out_ld, int64_t d0, float* tail, int64_t Rt, int64_t tpos,
+                           const float* vad, int32_t T, int32_t nf, float* vad_out, int64_t vad_ld, int64_t v0,
+                           void* stream) {
+  if (!win || !out || !tail) return fail(SEPVAD_E_ARG, "sepvad_live_stitch: null pointer");
+  if (B < 1 || B > INT32_MAX / 2 || H < 1 || H > N || N > win_ld)
+    return fail(SEPVAD_E_ARG, "sepvad_live_stitch: need B >= 1 and 1 <= H <= N <= win_ld");
+  if (H > Rt) return fail(SEPVAD_E_ARG, "sepvad_live_stitch: H must be <= Rt");
+  if (tpos < 0 || tpos >= Rt) return fail(SEPVAD_E_ARG, "sepvad_live_stitch: tpos must be in [0, Rt)");
+  if (d0 < 0 || d0 + H > out_ld) return fail(SEPVAD_E_ARG, "sepvad_live_stitch: d0 + H exceeds the output row");
+  if (vad) {
+    if (!vad_out) return fail(SEPVAD_E_ARG, "sepvad_live_stitch: vad without vad_out");
+    if (nf < 0 || nf > T) return fail(SEPVAD_E_ARG, "sepvad_live_stitch: nf must be in [0, T]");
+    if (v0 < 0 || v0 + nf > vad_ld) return fail(SEPVAD_E_ARG, "sepvad_live_stitch: v0 + nf exceeds the VAD row");
+  }
+  LiveStitchArgs a{};
+  a.B = B; a.H = H; a.win = win; a.win_ld = win_ld; a.s0 = N - H; a.perm = (const long long*)perm;
+  a.out = out; a.out_ld = out_ld; a.d0 = d0; a.tail = tail; a.Rt = Rt; a.tpos = tpos;
+  if (vad && nf > 0) {
+    a.vad = vad; a.vad_in_ld = T; a.f0 = T - nf; a.nf = nf; a.vad_out = vad_out; a.vad_ld = vad_ld; a.v0 = v0;
+  }
+  HIPCHK(launch_live_stitch(a, (hipStream_t)stream));
+  return SEPVAD_OK;
+}
+
 int32_t sepvad_resample_filter(int32_t orig_freq, int32_t new_freq, float* taps, int32_t cap, int32_t* info) {
   if (orig_freq < 1 || new_freq < 1 || !info) return fail(SEPVAD_E_ARG, "sepvad_resample_filter: bad arguments");
   // torchaudio.functional.functional._get_sinc_resample_kernel, sinc_interp_hann, width 6, rolloff 0.99

@@ -244,6 +244,32 @@ hipError_t launch_pit_l1(const PitArgs& a, hipStream_t s);
 hipError_t launch_pit_l1_sums(const PitArgs& a, double* sums, hipStream_t s);     // partials -> sums[4] (fixed order)
 hipError_t launch_pit_l1_choose(const PitArgs& a, const double* sums, double count, hipStream_t s);
 hipError_t launch_stream_append(const AppendArgs& a, hipStream_t s);
+// live sessions: PIT-L1 of every row on its own (row b == launch_pit_l1 on that row alone with B = 1, same bits).
+// a.nblk blocks per row, a.partial [B][nblk][4], a.perm_out [B][2], a.loss_out [B], a.pw_out [B][4]
+inline int pit_row_blocks(long long L) {  // the blocks launch_pit_l1 gets for one row of L samples
+  long long n = (L + 8191) / 8192;
+  return (int)(n < 1 ? 1 : n > PIT_MAX_BLOCKS ? PIT_MAX_BLOCKS : n);
+}
+hipError_t launch_pit_l1_rows(const PitArgs& a, hipStream_t s);
+struct RingPushArgs {          // mirrored ring [rows][2R]: sample j of the chunk at (pos + j) % R and again at + R
+  int rows;
+  long long n, R, pos;
+  const float* chunk; long long chunk_ld;
+  float* ring;
+};
+hipError_t launch_ring_push(const RingPushArgs& a, hipStream_t s);
+struct LiveStitchArgs {
+  int B;
+  long long H;                 // samples per speaker row: the window's last H
+  const float* win; long long win_ld, s0;   // [B][2][win_ld], the hop starts at s0
+  const long long* perm;       // nullable [B][2]
+  float* out; long long out_ld, d0;         // [B][2][out_ld]
+  float* tail; long long Rt, tpos;          // mirrored ring [B][2][2Rt]
+  const float* vad; long long vad_in_ld, f0;  // nullable [B][2][vad_in_ld], the frames start at f0
+  int nf;
+  float* vad_out; long long vad_ld, v0;     // [B][2][vad_ld]
+};
+hipError_t launch_live_stitch(const LiveStitchArgs& a, hipStream_t s);
 
 // input preprocessing (prep.hip)
 constexpr int NORM_MAX_BLOCKS = 1024;

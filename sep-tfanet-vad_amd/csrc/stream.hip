@@ -7,6 +7,12 @@
 //   k_stream_append  reorder_source_mse (model/combined_loss.py:63-78) fused with
 //       OnlineSaving.update_online_signal (online_class_unknown_targets.py:28-37): the reordered last
 //       hop of every window lands in its slot of the preallocated stitched signal (no torch.cat).
+// Live sessions (the same wrapper fed a chunk at a time, live.py):
+//   k_ring_push  get_truncated_signal (:39-41) on a mirrored input ring: the windows that are ready are read in place.
+//   k_pit_l1_rows_partial / k_pit_l1_rows_choose  the PIT above for every row on its own (the reference's semantics
+//       for a batch of ONE stream), through the same device functions: no second reduction order.
+//   k_live_stitch  k_stream_append's reorder into the caller's chunk and a mirrored tail ring (the only part of the
+//       stitched signal the next window's PIT reads, :87-91), plus the window's last VAD frames.
 // Layouts: signals are [B][2][ld] fp32 (speaker rows with stride ld). HBM-bound, no MFMA.
 // Reductions are deterministic: fixed per-block ranges, per-block partials in double, summed in
 // block order by k_pit_l1_sums; a sharded stream batch all-reduces those 4 sums before k_pit_l1_choose.
@@ -18,8 +24,7 @@ constexpr int PIT_THREADS = 256;
 
 // partial[blk][4] = sums over this block's (b, n) range of |est[b][e][n] - ref[b][t][n]|, (e, t) in
 // {(0,0), (0,1), (1,0), (1,1)} (pw_losses[:, est_idx, target_idx], model/pit_wrapper.py:172-177)
-__global__ __launch_bounds__(PIT_THREADS) void k_pit_l1_partial(PitArgs a) {
-  __shared__ float red[4 * 16];
+__device__ __forceinline__ void pit_partial(const PitArgs& a, float* red) {
   const long long total = (long long)a.B * a.L;
   const long long per = (total + gridDim.x - 1) / gridDim.x;
   const long long beg = per * blockIdx.x;
@@ -42,6 +47,31 @@ __global__ __launch_bounds__(PIT_THREADS) void k_pit_l1_partial(PitArgs a) {
     while (n >= a.L) { n -= a.L; ++b; }
   }
   block_reduce_store<4>(acc, red, a.partial + (size_t)blockIdx.x * 4);
+}
+
+__global__ __launch_bounds__(PIT_THREADS) void k_pit_l1_partial(PitArgs a) {
+  __shared__ float red[4 * 16];
+  pit_partial(a, red);
+}
+
+// Row blockIdx.y of a launch over rows as the B = 1 problem sepvad_pit_l1 would be given for that row alone
+__device__ __forceinline__ PitArgs pit_row_args(const PitArgs& a, int row) {
+  PitArgs r = a;
+  r.B = 1;
+  r.est = a.est + (size_t)row * 2 * a.est_ld;
+  r.ref = a.ref + (size_t)row * 2 * a.ref_ld;
+  r.partial = a.partial + (size_t)row * a.nblk * 4;
+  r.perm_out = a.perm_out ? a.perm_out + 2 * (size_t)row : nullptr;
+  r.loss_out = a.loss_out ? a.loss_out + row : nullptr;
+  r.pw_out = a.pw_out ? a.pw_out + 4 * (size_t)row : nullptr;
+  return r;
+}
+
+// PIT-L1 of every row on its own (live sessions): grid (nblk, B), the per-block body of the batch-global path on
+// each row's samples, so row b's partials are those of k_pit_l1_partial launched for that row with B = 1
+__global__ __launch_bounds__(PIT_THREADS) void k_pit_l1_rows_partial(PitArgs a) {
+  __shared__ float red[4 * 16];
+  pit_partial(pit_row_args(a, blockIdx.y), red);
 }
 
 // The pairwise L1 sums of this launch's rows: block partials summed in block order (sums[4], double). The partials are
@@ -111,6 +141,23 @@ __global__ __launch_bounds__(256) void k_pit_l1_sums_choose(PitArgs a, int nblk,
   pit_choose(a, tot, cnt);
 }
 
+// One block per row: k_pit_l1_sums_choose of that row alone (count = L)
+__global__ __launch_bounds__(256) void k_pit_l1_rows_choose(PitArgs a) {
+  __shared__ double part[PIT_MAX_BLOCKS * 4];
+  __shared__ double tot[4];
+  const PitArgs r = pit_row_args(a, blockIdx.x);
+  pit_block_sums(r, a.nblk, part, tot);
+  __syncthreads();
+  pit_choose(r, tot, (double)1 * (double)a.L);
+}
+
+hipError_t launch_pit_l1_rows(const PitArgs& a, hipStream_t s) {
+  if (a.B < 1 || a.B > 65535 || a.L < 1 || a.nblk != pit_row_blocks(a.L)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pit_l1_rows_partial, dim3(a.nblk, a.B), dim3(PIT_THREADS), 0, s, a);
+  hipLaunchKernelGGL(k_pit_l1_rows_choose, dim3(a.B), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_pit_l1_sums(const PitArgs& a, double* sums, hipStream_t s) {
   if (a.B < 1 || a.L < 1 || a.nblk < 1 || a.nblk > PIT_MAX_BLOCKS) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pit_l1_partial, dim3(a.nblk), dim3(PIT_THREADS), 0, s, a);
@@ -149,6 +196,71 @@ hipError_t launch_stream_append(const AppendArgs& a, hipStream_t s) {
   const long long nb = (total + 255) / 256;
   const int grid = (int)(nb < 4096 ? nb : 4096);
   hipLaunchKernelGGL(k_stream_append, dim3(grid), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---- live sessions: mirrored rings and the per-window stitch --------------------------------------------------------
+// dst[0, n) = src[0, n) by the whole block: float4 where both pointers are 16-byte aligned (the last n % 4 scalar),
+// scalar otherwise
+__device__ __forceinline__ void copy_run(float* dst, const float* src, long long n, long long tid, long long nth) {
+  if (n <= 0) return;
+  if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0) {
+    const long long n4 = n >> 2;
+    const float4* s4 = reinterpret_cast<const float4*>(src);
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    for (long long i = tid; i < n4; i += nth) d4[i] = s4[i];
+    for (long long i = (n4 << 2) + tid; i < n; i += nth) dst[i] = src[i];
+  } else {
+    for (long long i = tid; i < n; i += nth) dst[i] = src[i];
+  }
+}
+
+// n samples of src into the mirrored ring row [2R] at pos: the run up to the wrap and the run after it, each twice
+__device__ __forceinline__ void ring_store(float* ring, long long R, long long pos, const float* src, long long n,
+                                           long long tid, long long nth) {
+  const long long n1 = min(n, R - pos);
+  copy_run(ring + pos, src, n1, tid, nth);
+  copy_run(ring + R + pos, src, n1, tid, nth);
+  copy_run(ring, src + n1, n - n1, tid, nth);
+  copy_run(ring + R, src + n1, n - n1, tid, nth);
+}
+
+// grid (x, rows'): the blocks of one y share a row's samples, rows beyond gridDim.y by a stride loop
+__global__ __launch_bounds__(256) void k_ring_push(RingPushArgs a) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+  for (int r = blockIdx.y; r < a.rows; r += gridDim.y)
+    ring_store(a.ring + (size_t)r * 2 * a.R, a.R, a.pos, a.chunk + (size_t)r * a.chunk_ld, a.n, tid, nth);
+}
+
+static dim3 row_grid(long long n, long long rows) {
+  const long long nb = (n + 1023) / 1024;  // up to one float4 per thread and pass
+  return dim3((unsigned)(nb < 1 ? 1 : nb > 64 ? 64 : nb), (unsigned)(rows < 65535 ? rows : 65535));
+}
+
+hipError_t launch_ring_push(const RingPushArgs& a, hipStream_t s) {
+  if (a.rows < 1 || a.n < 1 || a.n > a.R || a.pos < 0 || a.pos >= a.R || a.chunk_ld < a.n) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_ring_push, row_grid(a.n, a.rows), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// Row (b, i) takes speaker p = perm[b][i] of the window: its last hop to the output chunk and to the tail ring, its
+// last frames to the VAD track
+__global__ __launch_bounds__(256) void k_live_stitch(LiveStitchArgs a) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+  for (int row = blockIdx.y; row < 2 * a.B; row += gridDim.y) {
+    const int b = row >> 1, i = row & 1;
+    const int p = a.perm ? (int)a.perm[2 * b + i] : i;
+    const float* src = a.win + ((size_t)b * 2 + p) * a.win_ld + a.s0;
+    copy_run(a.out + (size_t)row * a.out_ld + a.d0, src, a.H, tid, nth);
+    ring_store(a.tail + (size_t)row * 2 * a.Rt, a.Rt, a.tpos, src, a.H, tid, nth);
+    if (a.vad)
+      copy_run(a.vad_out + (size_t)row * a.vad_ld + a.v0, a.vad + ((size_t)b * 2 + p) * a.vad_in_ld + a.f0, a.nf, tid, nth);
+  }
+}
+
+hipError_t launch_live_stitch(const LiveStitchArgs& a, hipStream_t s) {
+  if (a.B < 1 || a.H < 1 || a.H > a.Rt || a.tpos < 0 || a.tpos >= a.Rt || a.nf < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_live_stitch, row_grid(a.H, 2LL * a.B), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

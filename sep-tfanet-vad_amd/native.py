@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "sepvad_stft_gate_test", "sepvad_istft_pair_test",
     "sepvad_stft", "sepvad_istft",
     "sepvad_pit_l1", "sepvad_stream_append",
+    "sepvad_ring_push", "sepvad_pit_l1_rows_scratch_bytes", "sepvad_pit_l1_rows", "sepvad_live_stitch",
     "sepvad_resample_filter", "sepvad_resample", "sepvad_normalize", "sepvad_si_sdr", "sepvad_vad_accuracy",
     "sepvad_snr", "sepvad_stoi_filter", "sepvad_stoi_scratch_bytes", "sepvad_stoi",
     "sepvad_rir_generate",
@@ -140,6 +141,14 @@ def load_library(path: str = LIB_PATH):
     lib.sepvad_pit_l1.argtypes = [P, i64, P, i64, i32, i64, P, P, P, P, P]
     lib.sepvad_stream_append.restype = i32
     lib.sepvad_stream_append.argtypes = [P, i64, i64, i32, i64, P, P, i64, i64, P]
+    lib.sepvad_ring_push.restype = i32
+    lib.sepvad_ring_push.argtypes = [P, i64, i32, i64, P, i64, i64, P]
+    lib.sepvad_pit_l1_rows_scratch_bytes.restype = i64
+    lib.sepvad_pit_l1_rows_scratch_bytes.argtypes = [i32, i64]
+    lib.sepvad_pit_l1_rows.restype = i32
+    lib.sepvad_pit_l1_rows.argtypes = [P, i64, P, i64, i32, i64, P, i64, P, P, P, P]
+    lib.sepvad_live_stitch.restype = i32
+    lib.sepvad_live_stitch.argtypes = [P, i64, i64, i32, i64, P, P, i64, i64, P, i64, i64, P, i32, i32, P, i64, i64, P]
     lib.sepvad_resample_filter.restype = i32
     lib.sepvad_resample_filter.argtypes = [i32, i32, P, i32, P]
     lib.sepvad_resample.restype = i32
@@ -349,9 +358,12 @@ class Handle:
             res.update(spectrum=spectrum, masks_b=masks_b, mask_per_speaker=mask)
         return res
 
-    def forward_windows(self, x: torch.Tensor, n_win: int, hop: int, N: int, inference_kw=None):
+    def forward_windows(self, x: torch.Tensor, n_win: int, hop: int, N: int, inference_kw=None,
+                        return_vad: bool = False):
         """Every streaming window in ONE forward (sepvad_forward_windows): window k of row b of x [B, L]
-        starts at sample k * hop; returns sep [n_win, B, num_spk, N] (window-major). No est is produced."""
+        starts at sample k * hop; returns sep [n_win, B, num_spk, N] (window-major). No est is produced.
+        return_vad: (sep, vad) with vad [n_win, B, num_spk, T] (the smoothed labels with return_smoothed_vad), or
+        None when the configuration has no VAD output."""
         if x.device.type != "cuda" or x.dtype != torch.float32 or x.stride(-1) != 1:
             raise RuntimeError("forward_windows: x must be a float32 ROCm tensor with unit sample stride")
         B = x.shape[0]
@@ -368,6 +380,8 @@ class Handle:
                "sepvad_forward_windows")
         if CHECK_EACH_FORWARD:
             self.fused_status()
+        if return_vad:
+            return sep, (vad.view(n_win, B, S, T) if vad is not None else None)
         return sep
 
     def side_outputs(self, stream: int, B: int, T: int, want=("spectrum", "masks_b", "mask_per_speaker"),

@@ -29,6 +29,7 @@ import torch
 
 from . import pit as _pit
 
+MAX_WINDOW_UTTS = 2048  # default of OnlineSaving.max_window_utts; live.py bounds its forwards by it too
 
 def _slice_bounds(length: int, start, stop):
     """Python slice semantics (negative indices, clamping) -> (begin, end)."""
@@ -52,7 +53,7 @@ class OnlineSaving:
         self.one_forward = True  # all windows in one forward when possible (False: the reference's window loop)
         # window-utterances per forward_windows call: long recordings run in window-major chunks, so the
         # workspace (~2.5 MB per window-utterance at T = 188) stays bounded (cfg 3: 1 792 in one call)
-        self.max_window_utts = 2048
+        self.max_window_utts = MAX_WINDOW_UTTS
         if criterion_similarity is not None:
             self.similarity = True
             self.criterion_similarity = criterion_similarity

@@ -71,6 +71,32 @@ def pit_l1(est: torch.Tensor, ref: torch.Tensor):
     return loss, perm, pw
 
 
+def pit_l1_rows(est: torch.Tensor, ref: torch.Tensor):
+    """pit_l1 of every row on its own (sepvad_pit_l1_rows): (loss [B], batch_indices [B, 2] int64, pairwise
+    [B, 2, 2]); row b has the bits of pit_l1(est[b:b+1], ref[b:b+1]). For independent live streams, whose
+    speakers must not be exchanged by what the other streams of the batch prefer."""
+    lib = _native.load_library()
+    if est.device.type != "cuda" or ref.device != est.device:
+        raise RuntimeError("pit_l1_rows: est and ref must be on the same ROCm device")
+    if est.shape != ref.shape:
+        raise ValueError(f"pit_l1_rows: shape mismatch {tuple(est.shape)} vs {tuple(ref.shape)}")
+    est, eld = _rows(est.float())
+    ref, rld = _rows(ref.float())
+    B, _, L = est.shape
+    dev = est.device
+    nbytes = int(lib.sepvad_pit_l1_rows_scratch_bytes(B, L))
+    if nbytes < 0:
+        _native._check(nbytes, "sepvad_pit_l1_rows_scratch_bytes")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    perm = torch.empty(B, 2, dtype=torch.int64, device=dev)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    pw = torch.empty(B, 2, 2, dtype=torch.float32, device=dev)
+    rc = lib.sepvad_pit_l1_rows(_native._ptr(est), eld, _native._ptr(ref), rld, B, L, _native._ptr(scratch), nbytes,
+                                _native._ptr(perm), _native._ptr(loss), _native._ptr(pw), _stream(dev))
+    _native._check(rc, "sepvad_pit_l1_rows")
+    return loss, perm, pw
+
+
 def pit_l1_sharded(est: torch.Tensor, ref: torch.Tensor, total_rows: int, group=None):
     """pit_l1 for a stream batch sharded over the ranks of `group` (total_rows streams over all ranks): the 4
     pairwise L1 sums of this rank's rows (sepvad_pit_l1_sums) are all-reduced (one 32-byte RCCL all-reduce,
