@@ -355,7 +355,7 @@ constexpr int PB_ATT = 4864;                                       // TF_Attenti
 constexpr int PB_A1 = 4884, PB_A2 = 4885;                          // PReLU slopes
 constexpr int PB_SX = 4886, PB_SXN = 4887;                         // fp16 range scale of this / the next block's x'
 constexpr int PB_WSUM = 4888;                                      // 5 doubles (8-byte aligned)
-constexpr int PB_EPS2 = 4898;                                      // reg2 eps, rescaled with d (see api.hip range guard)
+constexpr int PB_EPS2 = 4898;                                      // reg2 eps, rescaled with d (see pack.h range guard)
 constexpr int PB_SFC2 = 4899, PB_SB2 = 4900;                       // sum_c fc2[c], sum_c b2[c] (frame means of r)
 constexpr int PB_SIZE = 4904;                                      // multiple of 4 (float4 staging)
 // fp16 hi/lo weights of one block in MFMA fragment order: conv1d hi | lo (256x256) | res_out hi | lo (256x512)
@@ -417,8 +417,8 @@ struct TcnArgs {
 };
 hipError_t launch_tcn(const TcnArgs& a, int grid, hipStream_t s);
 int tcn_blocks_per_cu(int ln_mode, int prec, int lo, int nsl = 1);
-// host: float -> e4m3fn (OCP FP8, bias 7, max 448, no inf), round to nearest even, saturating
-uint8_t e4m3_rn(float x);
+// (the host's float -> e4m3fn conversion of the lo plane, round to nearest even and saturating, is pack.h
+// e4m3_rn)
 
 hipError_t launch_gemm(const GemmArgs& a, int ep, hipStream_t s);
 hipError_t launch_dw_stats(const DwStatsArgs& a, hipStream_t s);

@@ -142,7 +142,7 @@ static_assert(16 * FR * HEAD_VAD_N + 8 * FR * 32 <= (FR2 + 8) * CH && 4 * FG_WAV
 template <int NSL> struct SmemOf { using type = TcnSmem; };
 template <> struct SmemOf<2> { using type = TcnSmem2; };
 
-// Weight-blob layout per operand format (api.hip init_fused): fp16x3 hi/lo planes, or one plane.
+// Weight-blob layout per operand format (pack.h pack_fused): fp16x3 hi/lo planes, or one plane.
 // PREC_F32: one fp32 plane per GEMM (WS32_*, in __half units of the blob pointer), 2 KB per wave per K step.
 template <int PRE, int LQ = 0>
 struct WLay {
@@ -675,7 +675,7 @@ __global__ __launch_bounds__(NTHR) void k_tcn(TcnArgs a) {
         else f(std::integral_constant<int, 8 * NSL>{});
       };
       const int li = bi % a.layer;
-      const int dil = li == 0 ? 1 : (li % 4 + 1);   // model/model.py:285-295 (as api.hip packs it)
+      const int dil = li == 0 ? 1 : (li % 4 + 1);   // model/model.py:285-295 (as pack.h packs it)
       const float* pm = sm.prm;
       // this block's parameters: loads issued now (behind the already-landed weight prefetch), stored
       // into LDS after the conv1d GEMM

@@ -11,7 +11,7 @@
   stream; a stream's context can be released;
 * a batch split over several persistent launches (launch salts, epoch counters) is bitwise equal to one;
 * the fp16 split of the GEMM operands keeps fp32-equivalent accuracy when weights or inputs are scaled
-  by 1e-3 or 1e3 (static power-of-two range scales, api.hip range_exp).
+  by 1e-3 or 1e3 (static power-of-two range scales, pack.h range_exp).
 """
 import os
 
@@ -384,7 +384,7 @@ def test_salt_wrap_restarts_giveup_words(net):
 
 def test_concurrent_long_forwards_make_progress(net):
     """Three streams of one handle forwarding B=2 x 60 s files at once (T = 3751: groups of 118 workgroups, more than
-    half the chip each): the big persistent launches are ordered across streams (api.hip tcn_order_big), so none
+    half the chip each): the big persistent launches are ordered across streams (forward.hip tcn_launch_ordered), so none
     waits on a group that can never become resident. No give-up, every output equal to the serial run, fused."""
     from sep_tfanet_vad_amd import synth
     h = net.native_handle(DEV)
@@ -411,7 +411,7 @@ def test_concurrent_long_forwards_make_progress(net):
 
 def test_two_handles_concurrent_long_forwards(net, state_dicts):
     """Two handles on one device, each forwarding B=2 x 60 s files (groups of 118 workgroups, more than half the chip)
-    from its own host thread on its own stream, at once: the big-launch order (api.hip tcn_launch_ordered) is one
+    from its own host thread on its own stream, at once: the big-launch order (forward.hip tcn_launch_ordered) is one
     process-wide critical section (wait on the previous big launch, launch, record), so the two launches never run side
     by side holding partial groups. No give-up; each output equals its serial run."""
     import threading

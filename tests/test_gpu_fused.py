@@ -121,7 +121,7 @@ def test_persistent_groups_cover_large_batches(nets):
 
 
 def test_epoch_budget_small_stack(state_dicts, monkeypatch):
-    """Hand-off epochs of one launch (api.hip enqueue_chunk): 1 + per utterance 4 per block + 1 for the output head's
+    """Hand-off epochs of one launch (forward.hip tcn_fused): 1 + per utterance 4 per block + 1 for the output head's
     P5 round, below 2^12. A 2-block stack (layer 2, stack 1) with 8 groups per launch (SEPVAD_TCN_MAX_GROUPS) and
     SEPVAD_TCN_MAX_ITER unset: each group takes max_iter = 4094 // 9 = 454 utterances per launch, and the batch needs a
     second launch, whose tags the first would have repeated under the round-4 budget (4094 // 8 = 511 utterances:
@@ -206,7 +206,7 @@ def test_two_slices_bitwise_other_configs(variant, N, monkeypatch):
 
 @pytest.mark.parametrize("N", [32000, 130816])
 def test_two_slices_int8_and_fp16_lo_planes_bitwise(N, nets, monkeypatch):
-    """Two-slice workgroups stream the int8 lo plane's values as fp16 (api.hip twfq: no widening VALU beside the MFMAs);
+    """Two-slice workgroups stream the int8 lo plane's values as fp16 (pack.h WSET_X3_Q16: no widening VALU beside the MFMAs);
     SEPVAD_TCN_WQ16=0 streams the int8 bytes and widens them in registers (exact). Same MFMA operands: equal bits."""
     from sep_tfanet_vad_amd import synth
     x = torch.from_numpy(synth.make_batch(3, N, 4242)[0]).to(DEV)

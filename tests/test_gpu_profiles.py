@@ -1,7 +1,7 @@
 """Forward parity under weights whose statistics are not the recipe's, and on inputs with digital silence.
 
 Every other parity test draws its weights from synth.make_state_dict: positive weight-norm gains, PReLU slopes in
-(0.1, 0.35), GroupNorm gamma near 1, small beta and biases. The host packer (api.hip pack_pointwise: per-row power of
+(0.1, 0.35), GroupNorm gamma near 1, small beta and biases. The host packer (pack.h pack_pointwise: per-row power of
 two, absolute int8 lo steps, the mx == 0 branch), the range guard (gn_bound / range_exp), the folded GroupNorm 2
 (rstd (W'd - mean fc2)), the closed-form recursive LayerNorm (device_common.h recursive_moments), prelu2 and
 dbound *= max(1, |a2|) all depend on those statistics. The four profiles of tests/weight_profiles.py (signed, offset,

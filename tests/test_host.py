@@ -139,6 +139,16 @@ def test_e4m3_encoder_matches_torch():
     assert np.all(np.abs(back - lo) <= np.abs(lo) * 2.0 ** -4 + 2.0 ** -29)
 
 
+def test_packer_host_check():
+    """tools/pack_check.cpp, the stand-alone check of csrc/pack.h (no GPU): the fp16 split error, the int8 lo plane, the
+    fused TCN's blobs against the planes and parameters they are assembled from, and the packer's two errors."""
+    import subprocess
+    csrc = os.path.join(REPO, "sep-tfanet-vad_amd", "csrc")
+    r = subprocess.run(["make", "-C", csrc, "ARCH=gfx950", "pack_check"], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    assert "\nok\n" in r.stdout  # (after the digests: every case passed)
+
+
 def test_unknown_weight_lo_is_rejected(monkeypatch):
     """SEPVAD_WLO is validated in both layers (the C library refuses the same values at sepvad_create)."""
     import sep_tfanet_vad_amd as pkg

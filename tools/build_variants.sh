@@ -1,7 +1,7 @@
 # Build A/B variants of libsepvad.so that differ only in compile-time switches of the fused TCN (tcn_kernel.h) for the
 # production combination (fp16x3, int8 lo plane: build/fused_x3l2.o); every other object is the tree's own.
 # usage: bash tools/build_variants.sh name1="-DTCN_X=0" name2="-DTCN_Y=0 -DTCN_Z=0" ...   -> abl/lib_<name>.so
-# VARIANT_L0=1: the fp16-lo object too (build/fused_x3l0.o: the two-slice launches stream the int8 values as fp16, api.hip twfq)
+# VARIANT_L0=1: the fp16-lo object too (build/fused_x3l0.o: the two-slice launches stream the int8 values as fp16, pack.h WSET_X3_Q16)
 set -e
 cd "$(dirname "$0")/.."
 make -s -C sep-tfanet-vad_amd/csrc ARCH=gfx950

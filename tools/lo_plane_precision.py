@@ -2,7 +2,7 @@
 
 The fused TCN splits every pointwise weight (row-scaled by 2^-e, max |w| in [0.5, 1)) into fp16 hi + fp16 lo and
 issues A_lo B_hi + A_hi B_lo + A_hi B_hi. This emulates narrower lo planes on the CPU: effective weights
-(hi + q(lo)) / s in the oracle's conv1d / res_out (reg2 folded per column, as api.hip packs it), everything else
+(hi + q(lo)) / s in the oracle's conv1d / res_out (reg2 folded per column, as pack.h packs it), everything else
 fp32, and compares sep / VAD against the fp64 oracle next to the fp32 oracle's own error.
 usage: python tools/lo_plane_precision.py [B] [N]
 """
