@@ -350,6 +350,102 @@ int32_t sepvad_rir_generate(double c, double fs, const double* mics, int32_t n_m
                             int32_t high_pass, int32_t n_dim, int32_t order, int32_t n_samples, char mic_type,
                             double* out, int64_t cap);
 
+/* ---- reverberant scene simulation on the device (create_data/create_simulation_data.py) --------
+ * The entries below follow the metric entries: plain device pointers, row strides and optional index arrays,
+ * stream-ordered on the caller's hipStream_t, no allocation and no host synchronisation inside, ordinary kernel
+ * launches only. Every reduction has a fixed order: results are bitwise reproducible and a row's (job's, scene's)
+ * result does not depend on the batch around it.
+ *
+ * One microphone's response as the arguments of the host generator above (create_data/rirgen.cpp:115-131,
+ * create_simulation_data.py:258-291): beta holds n_beta = 1 (T60) or 6 values. */
+typedef struct SepVadRirDesc {
+  double c, fs;
+  double mic[3], src[3], room[3];
+  double beta[6];
+  double orientation[2];
+  int32_t n_beta, high_pass, n_dim, order, n_samples, mic_type; /* mic_type: the character code, e.g. 'o' */
+} SepVadRirDesc;
+
+/* The same job resolved (create_data/rirgen.cpp:133-199): the six reflection coefficients, the positions and the
+ * room in units of c/fs, the lattice bounds n_i = ceil(n_samples / (2 L_i)), the width Tw of the windowed sinc and
+ * the high-pass constants hp = {B1, B2, A1, R1}. */
+typedef struct SepVadRirJob {
+  double beta[6];
+  double s[3], r[3], L[3];
+  double cTs;
+  double angle[2];
+  double hp[4];
+  int32_t n_samples, n1, n2, n3, Tw, order, high_pass, mic_type;
+} SepVadRirJob;
+
+/* Largest lattice of one device job, counted in mirror images: 8 (2 n1 + 1)(2 n2 + 1)(2 n3 + 1). The value is that
+ * of a T60 = 1 s response (16 000 samples) of a 3 x 3 x 2.2 m room at 16 kHz, c = 340 m/s: n = (57, 57, 78). Every
+ * workgroup of the device generator walks its job's lattice once, so the cap bounds the longest kernel. Tw is
+ * capped at SEPVAD_RIR_MAX_TW (fs <= 64 kHz). */
+#define SEPVAD_RIR_MAX_IMAGES 16610600
+#define SEPVAD_RIR_MAX_TW 512
+
+/* HOST function: resolves n_jobs descriptions into jobs[n_jobs] in host double, with the code the host generator
+ * runs for its own prologue (csrc/rir_setup.h). Returns the largest n_samples of the table (>= 0), or SEPVAD_E_ARG
+ * (nothing usable written) under the host generator's conditions (c <= 0, fs <= 0, n_beta not 1 or 6, a negative
+ * length), for a lattice above SEPVAD_RIR_MAX_IMAGES or Tw above SEPVAD_RIR_MAX_TW, and for n_jobs outside
+ * 1..65535. */
+int32_t sepvad_rir_jobs_prepare(const SepVadRirDesc* desc, int32_t n_jobs, SepVadRirJob* jobs);
+
+/* HOST function: bytes of device scratch sepvad_rir_generate_device needs for n_jobs rows of ld doubles; negative
+ * for n_jobs < 1 or ld < 1. The generator keeps its image lists in LDS, so the answer is currently 0 and a null
+ * scratch is accepted; the pair stays in the signature as with the other entries. */
+int64_t sepvad_rir_scratch_bytes(int32_t n_jobs, int64_t ld);
+
+/* Replaces the generateRir calls of create_simulation_data.py:258-291 (create_data/rirgen.cpp:200-351) for a batch:
+ * jobs [n_jobs] (DEVICE copy of a prepared table), h [n_jobs][ld] double. Job j writes h[j][0 : n_samples_j] and
+ * zeroes the rest of its row (a job longer than ld is cut at ld). One workgroup per (job, 256 output samples) walks
+ * the lattice in the reference's loop order, keeps the images that touch its samples in that order, and one thread
+ * per sample sums their contributions in list order: the reference's summation order, no atomics. What decides a
+ * branch (the distance, its floor, the length, order and clipping tests) is computed in the host's operation order
+ * without FMA contraction and has the host's bits; gains, window and sinc use the device's pow / sin / cos
+ * (measured against the reference's goldens: DESIGN.md). The optional high-pass is the reference's two-pole
+ * recursion in its operation order, one lane per job. A table entry outside the caps above yields a zero row. */
+int32_t sepvad_rir_generate_device(const SepVadRirJob* jobs, int32_t n_jobs, double* h, int64_t ld, void* scratch,
+                                   int64_t scratch_bytes, void* stream);
+
+/* Replaces np.convolve(wave, h)[:cut_length] (create_simulation_data.py:482-500) for R rows:
+ *   y[r][n] = sum_{k=0}^{min(n, K_r - 1)} h[hidx[r]][k] * x[xidx[r]][n - k],  n < L,
+ * x float32 [.][x_ld] read as zero at and beyond Nx (widened to double exactly), h double [.][h_ld] with
+ * K_r = klen[hidx[r]] (device int32, clamped to 0..K; null: K for every row), y double [R][y_ld]; xidx / hidx
+ * nullable (identity). Each output is one fused-multiply-add chain over k ascending in double, whatever the tiling:
+ * bitwise reproducible, independent of R and of the other rows. */
+int32_t sepvad_fir_convolve(const float* x, int64_t x_ld, int64_t Nx, const double* h, int64_t h_ld, int32_t K,
+                            const int32_t* klen, const int32_t* xidx, const int32_t* hidx, int32_t R, int64_t L,
+                            double* y, int64_t y_ld, void* stream);
+
+/* Replaces the mixing and normalisation of create_simulation_data.py:558-588 with Noise.get_mixed (:707-713):
+ * mixed = sum_s rev[b][s] over rev [B][S][L] double (S <= 8, s ascending); with noise [B][L] float32 and snr_db [B]
+ * (both null, or both given; a NaN snr_db[b] leaves scene b without noise)
+ *   power_mode 0: gain = sqrt(10^(-snr/10) * std(mixed)^2 / std(noise)^2), numpy's population std (the reference);
+ *   power_mode 1: gain = sqrt(mean(mixed^2) / (mean(noise^2) * 10^(snr/10))) (synth.make_reverb_mixture);
+ * x = mixed + gain * noise, mix = a * (x - min) / (max - min) - b in that operation order, stored as float32 [B][L].
+ * (a, b) = (2, 1) in the reference, (1.8, 0.9) in only_inference.py:81. stats [B][4] double (nullable) receives
+ * {gain (0 without noise), min, max, a / (max - min)}. One workgroup per scene, double throughout. */
+int32_t sepvad_scene_mix(const double* rev, int32_t B, int32_t S, int64_t L, const float* noise,
+                         const double* snr_db, int32_t power_mode, double a, double b, float* mix, double* stats,
+                         void* stream);
+
+/* Targets of the same scenes from dry [B][S][L] double, out float32 [B][S][L]. mode 0: each row's own min-max with
+ * (a, b) (create_simulation_data.py:605-620); mode 1: stats[b][3] * dry, the mixture's scale without offset
+ * (synth.make_reverb_mixture: the targets stay SI-SDR-comparable with the mixture; stats from the entry above). */
+int32_t sepvad_scene_targets(const double* dry, int32_t B, int32_t S, int64_t L, int32_t mode, double a, double b,
+                             const double* stats, float* out, void* stream);
+
+/* Replaces convert_samples2frames_vad and the edge frames around it (create_data/vad_labels2stft_labels.py:14-23,
+ * 47-66): act [R][act_ld] uint8 sample-level activity with values 0..8 (larger values are not counted), L a multiple
+ * of 512; out [R][T] float32, T = 2 L / 512 + 1 (the model's 1 + N / 256, so the result feeds the VAD accuracy
+ * entry). Frame j = 1..T-2 is the most frequent value of act[256 (j-1) : 256 (j-1) + 512], the lowest value
+ * winning ties (argmax of bincount). Edge frames 0 and T-1 look at the first / last 256 samples: edge_mode 0 counts
+ * 256 zeros with them (the per-speaker rule, :52-56), edge_mode 1 the samples alone (the sum-track rule, :62-66). */
+int32_t sepvad_vad_frame_labels(const uint8_t* act, int64_t act_ld, int32_t R, int64_t L, int32_t edge_mode,
+                                float* out, void* stream);
+
 /* ---- input preprocessing of the reference CLI (only_inference.py:68-83) ---------------------
  * Windowed-sinc resampling filter of torchaudio.transforms.Resample(orig_freq, new_freq) with its
  * defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), host-side, double precision

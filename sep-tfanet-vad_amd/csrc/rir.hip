@@ -17,12 +17,11 @@
 #include <vector>
 
 #include "../../include/sepvad.h"
+#include "rir_setup.h"
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
-
-long round_half_away(double x) { return x >= 0 ? (long)(x + 0.5) : (long)(x - 0.5); }
+constexpr double kPi = sepvad::kRirPi;
 
 double sinc_d(double x) { return x == 0 ? 1.0 : std::sin(x) / x; }
 
@@ -49,47 +48,22 @@ extern "C" int32_t sepvad_rir_generate(double c, double fs, const double* mics, 
                                        const double* room, const double* beta_in, int32_t n_beta,
                                        const double* orientation, int32_t high_pass, int32_t n_dim, int32_t order,
                                        int32_t n_samples, char mic_type, double* out, int64_t cap) {
-  if (!mics || !src || !room || !beta_in || n_mics < 1 || (n_beta != 1 && n_beta != 6) || c <= 0 || fs <= 0)
-    return SEPVAD_E_ARG;
-  double beta[6];
-  double t60 = 0.0;
-  if (n_beta == 1) {
-    const double V = room[0] * room[1] * room[2];
-    const double S = 2 * (room[0] * room[2] + room[1] * room[2] + room[0] * room[1]);
-    t60 = beta_in[0];
-    if (t60 != 0) {
-      const double alfa = 24 * V * std::log(10.0) / (c * S * t60);
-      for (double& b : beta) b = std::sqrt(1 - alfa);
-    } else {
-      for (double& b : beta) b = 0;
-    }
-  } else {
-    for (int i = 0; i < 6; ++i) beta[i] = beta_in[i];
-  }
-  const double angle[2] = {orientation ? orientation[0] : 0.0, orientation ? orientation[1] : 0.0};
-  if (n_dim == 2) beta[4] = beta[5] = 0;
-  if (n_samples == -1) {
-    if (n_beta > 1) {
-      const double V = room[0] * room[1] * room[2];
-      const double alpha = ((1 - std::pow(beta[0], 2)) + (1 - std::pow(beta[1], 2))) * room[1] * room[2] +
-                           ((1 - std::pow(beta[2], 2)) + (1 - std::pow(beta[3], 2))) * room[0] * room[2] +
-                           ((1 - std::pow(beta[4], 2)) + (1 - std::pow(beta[5], 2))) * room[0] * room[1];
-      t60 = 24 * std::log(10.0) * V / (c * alpha);
-      if (t60 < 0.128) t60 = 0.128;
-    }
-    n_samples = (int)(t60 * fs);
-  }
-  if (n_samples < 0) return SEPVAD_E_ARG;
+  if (!mics || n_mics < 1) return SEPVAD_E_ARG;
+  sepvad::RirSetup st;
+  const int32_t rc = sepvad::rir_setup(c, fs, src, room, beta_in, n_beta, orientation, n_dim, n_samples, st);
+  if (rc < 0) return rc;
+  n_samples = st.n_samples;
   if (!out) return n_samples;  // size query
   if (cap < (int64_t)n_mics * n_samples) return SEPVAD_E_ARG;
 
-  const int Tw = 2 * (int)round_half_away(0.004 * fs);
-  const double cTs = c / fs, Fc = 1.0;
-  const double s[3] = {src[0] / cTs, src[1] / cTs, src[2] / cTs};
-  const double L[3] = {room[0] / cTs, room[1] / cTs, room[2] / cTs};
+  const double* beta = st.beta;
+  const double* angle = st.angle;
+  const int Tw = st.Tw;
+  const double cTs = st.cTs, Fc = 1.0;
+  const double* s = st.s;
+  const double* L = st.L;
   std::vector<double> lpi(Tw);
-  // high-pass filter constants (cut-off 100 Hz)
-  const double W = 2 * kPi * 100 / fs, R1 = std::exp(-W), B1 = 2 * R1 * std::cos(W), B2 = -R1 * R1, A1 = -(1 + R1);
+  const double R1 = st.R1, B1 = st.B1, B2 = st.B2, A1 = st.A1;
 
   for (int im = 0; im < n_mics; ++im) {
     double* h = out + (size_t)im * n_samples;
@@ -142,4 +116,45 @@ extern "C" int32_t sepvad_rir_generate(double c, double fs, const double* mics, 
     }
   }
   return n_samples;
+}
+
+// Job tables of the device generator (sim.hip): the prologue above per microphone, plus the lattice bounds the
+// host loop computes per microphone and the caps that bound a device job.
+extern "C" int32_t sepvad_rir_jobs_prepare(const SepVadRirDesc* desc, int32_t n_jobs, SepVadRirJob* jobs) {
+  if (!desc || !jobs || n_jobs < 1 || n_jobs > 65535) return SEPVAD_E_ARG;
+  int32_t n_max = 0;
+  for (int32_t j = 0; j < n_jobs; ++j) {
+    const SepVadRirDesc& d = desc[j];
+    sepvad::RirSetup st;
+    const int32_t rc = sepvad::rir_setup(d.c, d.fs, d.src, d.room, d.beta, d.n_beta, d.orientation, d.n_dim,
+                                         d.n_samples, st);
+    if (rc < 0) return rc;
+    SepVadRirJob& o = jobs[j];
+    for (int i = 0; i < 6; ++i) o.beta[i] = st.beta[i];
+    for (int i = 0; i < 3; ++i) {
+      o.s[i] = st.s[i];
+      o.r[i] = d.mic[i] / st.cTs;
+      o.L[i] = st.L[i];
+    }
+    o.cTs = st.cTs;
+    o.angle[0] = st.angle[0];
+    o.angle[1] = st.angle[1];
+    o.hp[0] = st.B1; o.hp[1] = st.B2; o.hp[2] = st.A1; o.hp[3] = st.R1;
+    const double nb[3] = {std::ceil(st.n_samples / (2 * st.L[0])), std::ceil(st.n_samples / (2 * st.L[1])),
+                          std::ceil(st.n_samples / (2 * st.L[2]))};
+    double images = 8.0;
+    for (int i = 0; i < 3; ++i) {
+      if (!(nb[i] >= 0 && nb[i] <= 1e6)) return SEPVAD_E_ARG;  // a room of no extent (or NaN) gives no lattice
+      images *= 2 * nb[i] + 1;
+    }
+    if (images > (double)SEPVAD_RIR_MAX_IMAGES || st.Tw > SEPVAD_RIR_MAX_TW || st.Tw < 0) return SEPVAD_E_ARG;
+    o.n_samples = st.n_samples;
+    o.n1 = (int)nb[0]; o.n2 = (int)nb[1]; o.n3 = (int)nb[2];
+    o.Tw = st.Tw;
+    o.order = d.order;
+    o.high_pass = d.high_pass == 1;
+    o.mic_type = d.mic_type;
+    if (st.n_samples > n_max) n_max = st.n_samples;
+  }
+  return n_max;
 }

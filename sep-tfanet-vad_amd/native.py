@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = (
     "sepvad_resample_filter", "sepvad_resample", "sepvad_normalize", "sepvad_si_sdr", "sepvad_vad_accuracy",
     "sepvad_snr", "sepvad_stoi_filter", "sepvad_stoi_scratch_bytes", "sepvad_stoi",
     "sepvad_rir_generate",
+    "sepvad_rir_jobs_prepare", "sepvad_rir_scratch_bytes", "sepvad_rir_generate_device", "sepvad_fir_convolve",
+    "sepvad_scene_mix", "sepvad_scene_targets", "sepvad_vad_frame_labels",
     "sepvad_set_timing", "sepvad_timing", "sepvad_destroy", "sepvad_last_error", "sepvad_abi_version",
     "sepvad_build_id",
 )
@@ -67,6 +69,26 @@ class SepVadOutputs(ctypes.Structure):
     _fields_ = [("sep", ctypes.c_void_p), ("vad", ctypes.c_void_p), ("est", ctypes.c_void_p),
                 ("spectrum", ctypes.c_void_p), ("masks_b", ctypes.c_void_p), ("mask", ctypes.c_void_p)]
 
+
+class SepVadRirDesc(ctypes.Structure):
+    """One microphone's response as the arguments of sepvad_rir_generate (include/sepvad.h)."""
+    _fields_ = [("c", ctypes.c_double), ("fs", ctypes.c_double), ("mic", ctypes.c_double * 3),
+                ("src", ctypes.c_double * 3), ("room", ctypes.c_double * 3), ("beta", ctypes.c_double * 6),
+                ("orientation", ctypes.c_double * 2), ("n_beta", ctypes.c_int32), ("high_pass", ctypes.c_int32),
+                ("n_dim", ctypes.c_int32), ("order", ctypes.c_int32), ("n_samples", ctypes.c_int32),
+                ("mic_type", ctypes.c_int32)]
+
+
+class SepVadRirJob(ctypes.Structure):
+    """The resolved job table entry the device generator reads (include/sepvad.h)."""
+    _fields_ = [("beta", ctypes.c_double * 6), ("s", ctypes.c_double * 3), ("r", ctypes.c_double * 3),
+                ("L", ctypes.c_double * 3), ("cTs", ctypes.c_double), ("angle", ctypes.c_double * 2),
+                ("hp", ctypes.c_double * 4), ("n_samples", ctypes.c_int32), ("n1", ctypes.c_int32),
+                ("n2", ctypes.c_int32), ("n3", ctypes.c_int32), ("Tw", ctypes.c_int32), ("order", ctypes.c_int32),
+                ("high_pass", ctypes.c_int32), ("mic_type", ctypes.c_int32)]
+
+
+RIR_MAX_IMAGES = 16610600  # SEPVAD_RIR_MAX_IMAGES
 
 _lib = None
 
@@ -171,6 +193,21 @@ def load_library(path: str = LIB_PATH):
     lib.sepvad_rir_generate.restype = i32
     lib.sepvad_rir_generate.argtypes = [ctypes.c_double, ctypes.c_double, dptr, i32, dptr, dptr, dptr, i32, dptr,
                                         i32, i32, i32, i32, ctypes.c_char, dptr, i64]
+    dbl = ctypes.c_double
+    lib.sepvad_rir_jobs_prepare.restype = i32
+    lib.sepvad_rir_jobs_prepare.argtypes = [ctypes.POINTER(SepVadRirDesc), i32, ctypes.POINTER(SepVadRirJob)]
+    lib.sepvad_rir_scratch_bytes.restype = i64
+    lib.sepvad_rir_scratch_bytes.argtypes = [i32, i64]
+    lib.sepvad_rir_generate_device.restype = i32
+    lib.sepvad_rir_generate_device.argtypes = [P, i32, P, i64, P, i64, P]
+    lib.sepvad_fir_convolve.restype = i32
+    lib.sepvad_fir_convolve.argtypes = [P, i64, i64, P, i64, i32, P, P, P, i32, i64, P, i64, P]
+    lib.sepvad_scene_mix.restype = i32
+    lib.sepvad_scene_mix.argtypes = [P, i32, i32, i64, P, P, i32, dbl, dbl, P, P, P]
+    lib.sepvad_scene_targets.restype = i32
+    lib.sepvad_scene_targets.argtypes = [P, i32, i32, i64, i32, dbl, dbl, P, P, P]
+    lib.sepvad_vad_frame_labels.restype = i32
+    lib.sepvad_vad_frame_labels.argtypes = [P, i64, i32, i64, i32, P, P]
     lib.sepvad_set_timing.restype = i32
     lib.sepvad_set_timing.argtypes = [P, i32]
     lib.sepvad_timing.restype = i32

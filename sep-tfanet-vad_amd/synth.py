@@ -159,3 +159,49 @@ def make_reverb_batch(batch: int, n_samples: int, base_seed: int = 4096, **kw):
     with ThreadPoolExecutor(max_workers=8) as ex:
         res = list(ex.map(lambda b: make_reverb_mixture(n_samples, base_seed + b, **kw), range(batch)))
     return np.stack([r[0] for r in res]), np.stack([r[1] for r in res])
+
+
+def _reverb_scene_draws(n_samples: int, seed: int, fs: int = FS, rt60=(0.2, 0.6), rir_samples: int | None = None):
+    """The host side of make_reverb_mixture, draw for draw: room, microphone, T60, the two unit-power sources with
+    their positions, the SNR and the coloured noise (float64)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    room = rng.uniform([3.0, 3.0, 2.2], [8.0, 7.0, 3.5])
+    mic = rng.uniform(0.2, 0.8, 3) * room
+    t60 = float(rng.uniform(*rt60))
+    n_rir = rir_samples or int(t60 * fs)
+    srcs, pos = [], []
+    for _ in range(2):
+        s = _source(rng, n_samples, fs)
+        s /= np.sqrt(np.mean(s ** 2)) + 1e-9
+        srcs.append(s)
+        pos.append(rng.uniform(0.15, 0.85, 3) * room)
+    snr = rng.uniform(0.0, 15.0)
+    noise = _ar1_noise(rng, n_samples, rng.uniform(0.3, 0.9))
+    return dict(room=room, mic=mic, t60=t60, n_rir=n_rir, sources=srcs, pos=pos, snr=snr, noise=noise)
+
+
+def make_reverb_batch_device(batch: int, n_samples: int, base_seed: int = 4096, device="cuda", **kw):
+    """make_reverb_batch with the heavy stages on the device: the same PCG64 draws in the same order (rooms,
+    positions, sources and noise stay on the host), then the image-method responses, the convolutions, the mix at the
+    drawn SNR and the normalisation through simulate.simulate_scenes (csrc/sim.hip). Returns device tensors
+    (mix [B, N] f32, direct-path sources [B, 2, N] f32) equal to make_reverb_batch's arrays to float32 rounding: the
+    device convolves the float32-rounded sources and noise directly in double where the host uses an FFT."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from . import simulate
+    fs = kw.get("fs", FS)
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        draws = list(ex.map(lambda b: _reverb_scene_draws(n_samples, base_seed + b, **kw), range(batch)))
+    rir_jobs, dry_jobs = [], []
+    for d in draws:
+        for p in d["pos"]:
+            job = dict(roomMeasures=list(d["room"]), sourcePosition=list(p), receiverPositions=list(d["mic"]), fs=fs,
+                       nSamples=d["n_rir"])
+            rir_jobs.append(dict(job, reverbTime=d["t60"]))
+            dry_jobs.append(dict(job, reverbTime=0.0))
+    src = torch.from_numpy(np.stack([np.stack(d["sources"]) for d in draws]).astype(np.float32)).to(device)
+    noise = torch.from_numpy(np.stack([d["noise"] for d in draws]).astype(np.float32)).to(device)
+    snr = torch.tensor([d["snr"] for d in draws], dtype=torch.float64).to(device)
+    mix, targets, _, _ = simulate.simulate_scenes(src, rir_jobs, dry_jobs, noise=noise, snr_db=snr, a=1.8, b=0.9,
+                                                  target_mode=1, power_mode=1)
+    return mix, targets
