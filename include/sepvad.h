@@ -337,6 +337,68 @@ int32_t sepvad_stoi(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, 
 int32_t sepvad_vad_accuracy(float* preds, const float* targets, int32_t B, int32_t S, int32_t T, int32_t in_place,
                             float* out, void* stream);
 
+/* ---- the evaluation criterion of test.py (test.py:49-64 builds it, :129-172 uses it) ----------------
+ * One pass over the five rows of every utterance (two estimates, two targets, the mixture) gives 16 double
+ * moments; every separation number of a test.py step is a closed form of them (csrc/eval.hip). */
+enum { SEPVAD_SDR_SISDR = 0, SEPVAD_SDR_SDSDR = 1, SEPVAD_SDR_SNR = 2 };  /* PairwiseNegSDR's sdr_type */
+/* Columns of the per-utterance score sheet (dB, float32, zero-mean, eps = float32 epsilon as sepvad_si_sdr). */
+enum {
+  SEPVAD_EV_SISDR0 = 0,      /* calc_sisdr(est reordered by perm, tgt)[b, 0]  (test.py:131-134) */
+  SEPVAD_EV_SISDR1,          /* ... [b, 1] */
+  SEPVAD_EV_SISDR_MIX0,      /* calc_sisdr(mix, tgt)[b, 0]  (test.py:139-142) */
+  SEPVAD_EV_SISDR_MIX1,
+  SEPVAD_EV_PIT_SISDR,       /* pit_si_sdr of utterance b: best permutation by mean SI-SDR (metric.py:258; test.py:151) */
+  SEPVAD_EV_PIT_SNR,         /* pit_snr of utterance b (metric.py:255-256) */
+  SEPVAD_EV_PIT_SISDR_MIX,   /* the same two with the mixture as both estimates (test.py:152) */
+  SEPVAD_EV_PIT_SNR_MIX,
+  SEPVAD_EV_COLS
+};
+/* means[4] of sepvad_eval_separation */
+enum { SEPVAD_EV_MEAN_LOSS = 0, SEPVAD_EV_MEAN_PIT_SISDR, SEPVAD_EV_MEAN_PIT_SNR, SEPVAD_EV_MEAN_SI_SDRI };
+
+/* HOST query: bytes of device scratch sepvad_eval_separation needs for B utterances of N samples (SEPVAD_E_ARG
+ * for B < 1, B > 65535, N < 1 or N > 2^40). Monotone in B and in N. */
+int64_t sepvad_eval_scratch_bytes(int32_t B, int64_t N);
+
+/* Replaces PITLossWrapper(PairwiseNegSDR(sdr_type, zero_mean, take_log, EPS), pit_from="pw_mtx") (model/sdr.py:48-86,
+ * model/pit_wrapper.py:100-145,287-312; built by test.py:49-56, called through CombinedLoss at test.py:129-130) and
+ * the separation metrics of the same step: calc_sisdr of the reordered estimates and of the mixture (test.py:134,142),
+ * pit_si_sdr / pit_snr of both (test.py:149-152, model/metric.py:255-258) and si_sdri (test.py:179-181,
+ * model/metric.py:145-160). est, tgt: [B][2][ld] rows of N samples with unit sample stride (speaker stride ld, batch
+ * stride 2 ld, as sepvad_pit_l1_rows); mix: [B][mix_ld], nullable (its moments are then 0 and the mixture columns
+ * are those of a silent mixture). Outputs (device): pw[b][i][j] = loss of estimate i against target j;
+ * perm[b][j] = the estimate assigned to target j, (0,1) or (1,0), the identity on a tie; min_loss[b] = the chosen
+ * permutation's mean loss; sheet[b][SEPVAD_EV_COLS] (nullable); means = {mean min_loss, pit_si_sdr, pit_snr, si_sdri}.
+ * Sums in double in a fixed order, float32 on store: bitwise reproducible, and utterance b's outputs do not depend
+ * on B or on the rows' alignment. scratch: 8-byte aligned device memory of scratch_bytes >= the query above.
+ * SEPVAD_E_ARG (nothing launched) for a null pointer (mix and sheet excepted), B < 1, B > 65535, N < 1, N > 2^40, a
+ * row stride below N (mix_ld only with mix), an unknown sdr_type, a short scratch or a scratch pointer that is not
+ * 8-byte aligned. */
+int32_t sepvad_eval_separation(const float* est, int64_t est_ld, const float* tgt, int64_t tgt_ld, const float* mix,
+                               int64_t mix_ld, int32_t B, int64_t N, int32_t sdr_type, int32_t zero_mean,
+                               int32_t take_log, double eps, void* scratch, int64_t scratch_bytes, float* pw,
+                               float* min_loss, int64_t* perm, float* sheet, float* means, void* stream);
+
+/* Replaces BinaryCrossEntropyLoss_Mean (model/combined_loss.py:120-138) on the VAD track reordered by perm
+ * (combined_loss.py:109-110), the pairwise table behind pit_CE_vad (model/metric.py:264; model/pit_wrapper.py:172-177
+ * get_pw_losses), the per-speaker confusion_matrix(labels=[0., 1.]) of test.py:164,172 and calc_vad
+ * (Our_utils/utils_test.py:67-73) on the masks reordered by perm (test.py:148,170). vad, labels: contiguous
+ * [B][2][T] float32; labels equal to 2 count as 1 and, when fix_labels, are written back as 1 (the reference mutates
+ * its argument). perm: [B][2] int64 on the device, nullable (identity); pred[b][s] = vad[b][perm[b][s]].
+ *   bce_rows[b] = sum over s, t of w (-(y log p + (1 - y) log(1 - p))), w = 0.36 y + 0.64 (1 - y), logs clamped at
+ *                 -100; bce_mean = their mean over the batch;
+ *   pw_ce[i][j] = the same sum over the whole batch and all frames of vad[:, i] against labels[:, j];
+ *   conf[b][s]  = (tn, fp, fn, tp) of pred > 0.5 against the labels, pairs with a label other than 0 / 1 left out
+ *                 (a NaN pred is not > 0.5 and counts as prediction 0);
+ *   simple[b][s][t] (int64, with masks [B][2][257][T] post-sigmoid) = at least 65 of the 257 bins of
+ *                 masks[b][perm[b][s]][:, t] are >= 0.5; conf_simple (nullable) = its confusion counts.
+ * masks NULL: simple and conf_simple are not touched. vad and labels both NULL with masks and simple given: only
+ * simple is written. SEPVAD_E_ARG (nothing launched) for any other null pointer (perm, masks, simple without masks
+ * and conf_simple excepted), masks without simple, B < 1, B > 65535 or T < 1. */
+int32_t sepvad_eval_vad(const float* vad, float* labels, int32_t fix_labels, const int64_t* perm, const float* masks,
+                        int32_t B, int32_t T, float* bce_rows, float* bce_mean, float* pw_ce, int32_t* conf,
+                        int64_t* simple, int32_t* conf_simple, void* stream);
+
 /* ---- synthetic reverberant mixtures (BASELINE cfg 4): image-method room impulse responses --------
  * Replaces pyrirgen.generateRir / gen_rir (create_data/rirgen.cpp:115-351, create_data/pyrirgen.pyx)
  * as create_data/create_simulation_data.py:284-289 calls it. HOST function, double precision:

@@ -475,6 +475,58 @@ int32_t sepvad_vad_accuracy(float* preds, const float* targets, int32_t B, int32
   HIPRET(launch_vad_acc(a, (hipStream_t)stream));
 }
 
+static int64_t eval_chunks(int64_t N) { return (N + EV_CHUNK - 1) / EV_CHUNK; }
+static int64_t eval_scratch(int32_t B, int64_t N) {
+  return (int64_t)B * (eval_chunks(N) * EV_MOM + EV_ROWVALS) * (int64_t)sizeof(double);
+}
+
+int64_t sepvad_eval_scratch_bytes(int32_t B, int64_t N) {
+  if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40))
+    return fail(SEPVAD_E_ARG, "sepvad_eval_scratch_bytes: need 1 <= B <= 65535, 1 <= N <= 2^40");
+  return eval_scratch(B, N);
+}
+
+// PITLossWrapper(PairwiseNegSDR(...), "pw_mtx") (model/sdr.py:48-86, model/pit_wrapper.py:100-145,287-312) and the
+// separation scores of the same test.py step (test.py:129-152,179-181): csrc/eval.hip
+int32_t sepvad_eval_separation(const float* est, int64_t est_ld, const float* tgt, int64_t tgt_ld, const float* mix,
+                               int64_t mix_ld, int32_t B, int64_t N, int32_t sdr_type, int32_t zero_mean,
+                               int32_t take_log, double eps, void* scratch, int64_t scratch_bytes, float* pw,
+                               float* min_loss, int64_t* perm, float* sheet, float* means, void* stream) {
+  if (!est || !tgt || !scratch || !pw || !min_loss || !perm || !means)
+    return fail(SEPVAD_E_ARG, "sepvad_eval_separation: null pointer");
+  if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40)) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: need 1 <= B <= 65535, 1 <= N <= 2^40");
+  if (est_ld < N || tgt_ld < N || (mix && mix_ld < N)) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: row strides must be >= N");
+  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: unknown sdr_type");
+  if (scratch_bytes < eval_scratch(B, N)) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: scratch too small (sepvad_eval_scratch_bytes)");
+  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: scratch must be 8-byte aligned");
+  EvalSepArgs a{};
+  a.est = est; a.est_ld = est_ld; a.tgt = tgt; a.tgt_ld = tgt_ld; a.mix = mix; a.mix_ld = mix_ld;
+  a.B = B; a.N = N; a.nchunk = (int)eval_chunks(N);
+  a.sdr_type = sdr_type; a.zero_mean = zero_mean != 0; a.take_log = take_log != 0; a.eps = eps;
+  a.partial = (double*)scratch;
+  a.rowvals = a.partial + (int64_t)B * a.nchunk * EV_MOM;
+  a.pw = pw; a.min_loss = min_loss; a.perm = (long long*)perm; a.sheet = sheet; a.means = means;
+  HIPRET(launch_eval_separation(a, (hipStream_t)stream));
+}
+
+// BinaryCrossEntropyLoss_Mean (model/combined_loss.py:120-138), pit_CE_vad's pairwise table (model/metric.py:264),
+// the confusion counts of test.py:164,172 and calc_vad (Our_utils/utils_test.py:67-73): csrc/eval.hip
+int32_t sepvad_eval_vad(const float* vad, float* labels, int32_t fix_labels, const int64_t* perm, const float* masks,
+                        int32_t B, int32_t T, float* bce_rows, float* bce_mean, float* pw_ce, int32_t* conf,
+                        int64_t* simple, int32_t* conf_simple, void* stream) {
+  if (B < 1 || B > 65535 || T < 1) return fail(SEPVAD_E_ARG, "sepvad_eval_vad: need 1 <= B <= 65535, T >= 1");
+  const bool masks_only = !vad && !labels && masks && simple;
+  if (!masks_only && (!vad || !labels || !bce_rows || !bce_mean || !pw_ce || !conf))
+    return fail(SEPVAD_E_ARG, "sepvad_eval_vad: null pointer");
+  if (masks && !simple) return fail(SEPVAD_E_ARG, "sepvad_eval_vad: masks without simple");
+  EvalVadArgs a{};
+  a.vad = vad; a.labels = labels; a.fix_labels = fix_labels != 0; a.perm = (const long long*)perm; a.masks = masks;
+  a.B = B; a.T = T; a.bce_rows = bce_rows; a.bce_mean = bce_mean; a.pw_ce = pw_ce; a.conf = conf;
+  a.simple = masks ? (long long*)simple : nullptr;
+  a.conf_simple = masks && !masks_only ? conf_simple : nullptr;
+  HIPRET(launch_eval_vad(a, (hipStream_t)stream));
+}
+
 int32_t sepvad_normalize(const float* x, int64_t n, float* y, void* scratch, void* stream) {
   if (!x || !y || !scratch || n < 1) return fail(SEPVAD_E_ARG, "sepvad_normalize: bad arguments");
   static_assert(NORM_MAX_BLOCKS * 2 * sizeof(float) <= SEPVAD_NORM_SCRATCH_BYTES, "scratch size");

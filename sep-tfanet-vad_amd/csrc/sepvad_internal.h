@@ -331,6 +331,37 @@ struct VadAccArgs {
 hipError_t launch_vad_acc(const VadAccArgs& a, hipStream_t s);
 hipError_t launch_normalize(const NormArgs& a, hipStream_t s);
 
+// evaluation criterion (eval.hip): the 16 moments of one utterance's five rows, read once, and everything
+// test.py's step derives from them
+constexpr int EV_CHUNK = 4096;  // samples per workgroup of k_eval_moments (a multiple of 4: chunk bases keep the rows' alignment)
+constexpr int EV_MOM = 16;      // EVM_* below
+constexpr int EV_ROWVALS = 4;   // per-utterance doubles the batch means are taken over (after the partials in scratch)
+constexpr int EV_MASK_BINS = 257;
+struct EvalSepArgs {
+  const float* est; long long est_ld;   // [B][2][est_ld]
+  const float* tgt; long long tgt_ld;   // [B][2][tgt_ld]
+  const float* mix; long long mix_ld;   // [B][mix_ld], nullable
+  int B; long long N; int nchunk;       // nchunk = ceil(N / EV_CHUNK)
+  int sdr_type, zero_mean, take_log; double eps;
+  double* partial;                      // [B][nchunk][EV_MOM] scratch
+  double* rowvals;                      // [B][EV_ROWVALS] scratch
+  float* pw; float* min_loss; long long* perm;   // [B][2][2], [B], [B][2]
+  float* sheet;                         // [B][SEPVAD_EV_COLS], nullable
+  float* means;                         // [4]
+};
+hipError_t launch_eval_separation(const EvalSepArgs& a, hipStream_t s);
+struct EvalVadArgs {
+  const float* vad; float* labels;      // [B][2][T]; both null: only the calc_vad part runs
+  int fix_labels;
+  const long long* perm;                // [B][2], nullable (identity)
+  const float* masks;                   // [B][2][257][T], nullable
+  int B, T;
+  float* bce_rows; float* bce_mean; float* pw_ce;   // [B], [1], [2][2]
+  int* conf;                            // [B][2][4] (tn, fp, fn, tp)
+  long long* simple; int* conf_simple;  // [B][2][T]; [B][2][4], nullable
+};
+hipError_t launch_eval_vad(const EvalVadArgs& a, hipStream_t s);
+
 // ---- fused persistent TCN (tcn_kernel.h; dispatch fused.hip, instantiations fused_inst.hip) ----
 constexpr int FR = 32;          // frames per workgroup
 #ifndef SEPVAD_FG_MAX

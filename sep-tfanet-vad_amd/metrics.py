@@ -17,9 +17,12 @@
 * ``stoi`` (``model/stoi_metric.py:207-301``, classic STOI; ``extended=True`` draws ``np.random`` noise and is
   refused), the ``Stoi`` module and ``stoi_met`` (``model/metric.py:207-223,276-277``): every pair of a batch in one
   call of ``sepvad_stoi`` (csrc/stoi.hip), float64 results on the device, no host round trip.
+* ``pit_CE_vad`` (``model/metric.py:264-265``), ``vad_confusion`` (the per-speaker ``confusion_matrix`` of
+  ``test.py:164``) and ``calc_vad`` (``Our_utils/utils_test.py:67-73``): ``sepvad_eval_vad`` (csrc/eval.hip);
+  ``evaluate.score_batch`` returns all of a ``test.py`` step's numbers from one pass over the rows.
 
-All inputs are ROCm tensors; the arithmetic runs in ``k_si_sdr`` / ``k_snr`` (csrc/metrics.hip) and the ``k_stoi_*``
-kernels (csrc/stoi.hip) through the C ABI. There is no CPU fallback.
+All inputs are ROCm tensors; the arithmetic runs in ``k_si_sdr`` / ``k_snr`` (csrc/metrics.hip), the ``k_stoi_*``
+kernels (csrc/stoi.hip) and the ``k_eval_*`` kernels (csrc/eval.hip) through the C ABI. There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -248,3 +251,28 @@ class Accuracy_Vad(torch.nn.Module):
 
 vad_accuracy = Accuracy_Vad()  # model/metric.py:270-271
 vad_accuracy.__name__ = "vad_accuracy"
+
+# model/metric.py:264-265 (config["metrics"]["vad"], test.py:67,155-156); an nn.Module, so .to exists
+from .evaluate import BinaryCrossEntropyLoss_Mean as _BceMean  # noqa: E402
+from .pit import PITLossWrapper as _PITLossWrapper  # noqa: E402
+
+pit_CE_vad = _PITLossWrapper(loss_func=_BceMean(), pit_from="pw_pt")
+pit_CE_vad.__name__ = "pit_CE_vad"
+
+
+def vad_confusion(preds: torch.Tensor, labels: torch.Tensor, perm=None):
+    """The confusion_matrix(label, pred, labels=[0., 1.]).ravel() of test.py:164 for every utterance and speaker at
+    once: preds, labels [B, 2, T] -> [B, 2, 4] int32 (tn, fp, fn, tp) on the device. A prediction is 1 when
+    preds > 0.5 (Accuracy_Vad's rule; already thresholded 0 / 1 preds count as they are, a NaN as 0), labels equal to 2 count
+    as 1 (labels is not changed), pairs with any other label are left out; perm [B, 2] int64 (device) counts
+    preds[b, perm[b, s]] against labels[b, s]."""
+    from .evaluate import eval_vad
+    _check_same_shape(preds, labels)
+    return eval_vad(preds, labels, perm, fix_labels=False)["conf"]
+
+
+def calc_vad(masks: torch.Tensor):
+    """Our_utils/utils_test.py:67-73: post-sigmoid masks [B, 2, 257, T] -> [B, 2, T] int64, 1 where at least a
+    quarter of the bins (65 of 257) are >= 0.5."""
+    from .evaluate import simple_vad
+    return simple_vad(masks)

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "sepvad_ring_push", "sepvad_pit_l1_rows_scratch_bytes", "sepvad_pit_l1_rows", "sepvad_live_stitch",
     "sepvad_resample_filter", "sepvad_resample", "sepvad_normalize", "sepvad_si_sdr", "sepvad_vad_accuracy",
     "sepvad_snr", "sepvad_stoi_filter", "sepvad_stoi_scratch_bytes", "sepvad_stoi",
+    "sepvad_eval_scratch_bytes", "sepvad_eval_separation", "sepvad_eval_vad",
     "sepvad_rir_generate",
     "sepvad_rir_jobs_prepare", "sepvad_rir_scratch_bytes", "sepvad_rir_generate_device", "sepvad_fir_convolve",
     "sepvad_scene_mix", "sepvad_scene_targets", "sepvad_vad_frame_labels",
@@ -189,6 +190,13 @@ def load_library(path: str = LIB_PATH):
     lib.sepvad_stoi.argtypes = [P, i64, P, i64, i64, i32, P, P, i32, P, i64, P, P, P]
     lib.sepvad_vad_accuracy.restype = i32
     lib.sepvad_vad_accuracy.argtypes = [P, P, i32, i32, i32, i32, P, P]
+    lib.sepvad_eval_scratch_bytes.restype = i64
+    lib.sepvad_eval_scratch_bytes.argtypes = [i32, i64]
+    lib.sepvad_eval_separation.restype = i32
+    lib.sepvad_eval_separation.argtypes = [P, i64, P, i64, P, i64, i32, i64, i32, i32, i32, ctypes.c_double, P, i64,
+                                           P, P, P, P, P, P]
+    lib.sepvad_eval_vad.restype = i32
+    lib.sepvad_eval_vad.argtypes = [P, P, i32, P, P, i32, i32, P, P, P, P, P, P, P]
     dptr = ctypes.POINTER(ctypes.c_double)
     lib.sepvad_rir_generate.restype = i32
     lib.sepvad_rir_generate.argtypes = [ctypes.c_double, ctypes.c_double, dptr, i32, dptr, dptr, dptr, i32, dptr,

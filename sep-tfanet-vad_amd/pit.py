@@ -7,6 +7,9 @@ with ``return_incides=True`` (``model/online_class_unknown_targets.py:87-91``,
 The pairwise losses, the permutation choice and the reordering run in ``libsepvad.so``
 (``sepvad_pit_l1``, ``sepvad_stream_append``); there is no CPU path.
 
+``PITLossWrapper`` also carries the two criteria ``test.py:49-61`` builds for evaluation, pairwise negative SDR with
+``pw_mtx`` and the weighted VAD BCE with ``pw_pt`` (``sepvad_eval_separation``, ``sepvad_eval_vad``; ``evaluate.py``).
+
 Reference semantics kept on purpose: ``nn.L1Loss()`` (reduction="mean") reduces over the batch as
 well as the samples, so ``get_pw_losses`` (``pit_wrapper.py:172-177``) fills every batch row with the
 same scalar and the chosen permutation is shared by the whole batch.
@@ -155,9 +158,18 @@ def reorder_source_mse(preds: torch.Tensor, batch_indices: torch.Tensor) -> torc
 class PITLossWrapper(nn.Module):
     """``PITLossWrapper(loss_func, pit_from)`` (reference ``model/pit_wrapper.py:66-75``).
 
-    Natively supported: ``loss_func`` an ``nn.L1Loss`` with reduction "mean", ``pit_from="pw_pt"``,
-    two sources — the criterion the streaming wrapper is built with. Other combinations raise
-    ``NotImplementedError`` (training losses are out of scope).
+    Natively supported, for two sources:
+
+    * ``loss_func`` an ``nn.L1Loss`` with reduction "mean", ``pit_from="pw_pt"`` — the criterion the streaming
+      wrapper is built with;
+    * ``loss_func`` a ``sdr.PairwiseNegSDR``, ``pit_from="pw_mtx"`` — ``loss_separation`` of both shipped configs
+      (``test.py:49-56``): a permutation per utterance (``sepvad_eval_separation``);
+    * ``loss_func`` a ``combined_loss.BinaryCrossEntropyLoss_Mean``, ``pit_from="pw_pt"`` — ``loss_vad`` and
+      ``pit_CE_vad`` (``test.py:59-61``, ``model/metric.py:264``): that loss returns a scalar, so the permutation is
+      shared by the batch (``sepvad_eval_vad``), and its labels equal to 2 become 1 in place.
+
+    ``perm_reduce`` may be ``None`` or ``False`` (what ``test.py:50-54`` passes for the configs' ``false``). Other
+    combinations raise ``NotImplementedError`` (training losses are out of scope). Forward-only.
     """
 
     def __init__(self, loss_func, pit_from="pw_mtx", perm_reduce=None):
@@ -173,14 +185,36 @@ class PITLossWrapper(nn.Module):
         return (self.pit_from == "pw_pt" and self.perm_reduce is None and isinstance(self.loss_func, nn.L1Loss)
                 and self.loss_func.reduction == "mean")
 
+    def _criterion_forward(self, est_targets, targets, n_src, kwargs):
+        """(mean loss, batch_indices [B, 2] int64) of the two evaluation criteria of test.py:49-61."""
+        from .evaluate import BinaryCrossEntropyLoss_Mean, eval_vad
+        from .sdr import PairwiseNegSDR
+        plain = self.perm_reduce is None or self.perm_reduce is False
+        if plain and not kwargs and self.pit_from == "pw_mtx" and isinstance(self.loss_func, PairwiseNegSDR):
+            r = self.loss_func.evaluate(est_targets, targets)  # its TypeError / NotImplementedError on bad shapes
+            return r["means"][0], r["perm"]
+        if (plain and not kwargs and n_src == 2 and self.pit_from == "pw_pt"
+                and isinstance(self.loss_func, BinaryCrossEntropyLoss_Mean)):
+            pw = eval_vad(est_targets, targets)["pw_ce"]  # [est i][target j], every batch row of get_pw_losses
+            # find_best_perm_factorial (pit_wrapper.py:287-312) on that one matrix: float32 adds, the first minimum
+            # wins; a few scalar device ops, nothing read on the host
+            loss_id, loss_sw = (pw[0, 0] + pw[1, 1]) / 2, (pw[1, 0] + pw[0, 1]) / 2
+            swap = (loss_sw < loss_id).to(torch.int64)
+            ident = torch.arange(2, device=pw.device)
+            return torch.minimum(loss_id, loss_sw), (ident ^ swap).expand(targets.shape[0], 2).contiguous()
+        raise NotImplementedError("native PIT: built for 2 sources and PITLossWrapper(nn.L1Loss(), 'pw_pt'), "
+                                  "PITLossWrapper(sdr.PairwiseNegSDR(...), 'pw_mtx') or "
+                                  "PITLossWrapper(combined_loss.BinaryCrossEntropyLoss_Mean(), 'pw_pt'), without "
+                                  "perm_reduce or extra arguments")
+
     def forward(self, est_targets, targets, target_vad=0, return_est=False, return_incides=False,
                 reduce_kwargs=None, **kwargs):
         n_src = targets.shape[1]
         assert n_src < 10, f"Expected source axis along dim 1, found {n_src}"
-        if not self._native_ok() or n_src != 2 or kwargs:
-            raise NotImplementedError("native PIT: only PITLossWrapper(nn.L1Loss(), pit_from='pw_pt') with 2 "
-                                      "sources (the streaming wrapper's criterion) is built")
-        mean_loss, batch_indices, _ = pit_l1(est_targets, targets)
+        if self._native_ok() and n_src == 2 and not kwargs:
+            mean_loss, batch_indices, _ = pit_l1(est_targets, targets)
+        else:
+            mean_loss, batch_indices = self._criterion_forward(est_targets, targets, n_src, kwargs)
         if not return_est and not return_incides:
             return mean_loss
         if not return_est and return_incides:
