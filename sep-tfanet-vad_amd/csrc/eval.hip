@@ -15,6 +15,15 @@
 // double; k_eval_means takes the batch means. No atomics, every sum in a fixed order: results are bitwise
 // reproducible, and an utterance's numbers depend on its own rows and N only (not on B, and not on the rows'
 // alignment: the float4 and the scalar path give each thread the same samples in the same order).
+//
+// Conditioning. The zero-mean closed forms (<x',y'> = <x,y> - sum x sum y / N, <e,e> = al^2 <t,t> - 2 al <p,t> + <p,p>)
+// lose (mean^2 / variance) (signal / residual) of the moments' precision; on raw rows with a DC of 100 .. 1000 standard
+// deviations that is 1e-3 .. 1 dB at a 71 .. 78 dB residual. The sums are therefore those of the rows less their own
+// first sample (every chunk of a row subtracts the row's first sample, so the partials still add up): the centred
+// moments do not depend on the shift, the difference of two floats is exact in double, and what is left of the mean
+// is of the order of the row's standard deviation. zero_mean = 0 needs the raw moments: k_eval_finish takes the shift
+// out again in closed form (ev_raw), which costs rounding only. Measured table: DESIGN.md section 12,
+// tests/test_gpu_score_regimes.py.
 #include "device_common.h"
 #include "../../include/sepvad.h"
 
@@ -38,9 +47,11 @@ __device__ __forceinline__ void ev_load4(const float* p, int q, float (&v)[4]) {
   }
 }
 
-// explicit fma: the same rounding in both paths whatever the compiler contracts
-__device__ __forceinline__ void ev_acc(double (&s)[EV_MOM], float e0, float e1, float t0, float t1, float m) {
-  const double x0 = e0, x1 = e1, y0 = t0, y1 = t1, z = m;
+// explicit fma: the same rounding in both paths whatever the compiler contracts; c: the five rows' first samples
+__device__ __forceinline__ void ev_acc(double (&s)[EV_MOM], const double (&c)[5], float e0, float e1, float t0, float t1,
+                                       float m) {
+  const double x0 = (double)e0 - c[0], x1 = (double)e1 - c[1], y0 = (double)t0 - c[2], y1 = (double)t1 - c[3];
+  const double z = (double)m - c[4];
   s[EVM_S + 0] += x0; s[EVM_S + 1] += x1; s[EVM_S + 2] += y0; s[EVM_S + 3] += y1; s[EVM_S + 4] += z;
   s[EVM_Q + 0] = fma(x0, x0, s[EVM_Q + 0]); s[EVM_Q + 1] = fma(x1, x1, s[EVM_Q + 1]);
   s[EVM_Q + 2] = fma(y0, y0, s[EVM_Q + 2]); s[EVM_Q + 3] = fma(y1, y1, s[EVM_Q + 3]);
@@ -52,17 +63,17 @@ __device__ __forceinline__ void ev_acc(double (&s)[EV_MOM], float e0, float e1, 
 
 template <bool VEC>
 __device__ __forceinline__ void ev_chunk(const float* e0, const float* e1, const float* t0, const float* t1,
-                                         const float* m, int len, double (&s)[EV_MOM]) {
+                                         const float* m, int len, const double (&c)[5], double (&s)[EV_MOM]) {
   const int n4 = len / 4;
   for (int q = threadIdx.x; q < n4; q += EV_THREADS) {
-    float a[4], b[4], c[4], d[4], z[4];
-    ev_load4<VEC>(e0, q, a); ev_load4<VEC>(e1, q, b); ev_load4<VEC>(t0, q, c); ev_load4<VEC>(t1, q, d);
+    float a[4], b[4], g[4], d[4], z[4];
+    ev_load4<VEC>(e0, q, a); ev_load4<VEC>(e1, q, b); ev_load4<VEC>(t0, q, g); ev_load4<VEC>(t1, q, d);
     ev_load4<VEC>(m, q, z);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) ev_acc(s, a[k], b[k], c[k], d[k], z[k]);
+    for (int k = 0; k < 4; ++k) ev_acc(s, c, a[k], b[k], g[k], d[k], z[k]);
   }
   const int i = n4 * 4 + threadIdx.x;  // the chunk's last len % 4 samples: one each for threads 0 .. 2
-  if (i < len) ev_acc(s, e0[i], e1[i], t0[i], t1[i], m ? m[i] : 0.f);
+  if (i < len) ev_acc(s, c, e0[i], e1[i], t0[i], t1[i], m ? m[i] : 0.f);
 }
 
 // grid B * nchunk: workgroup b * nchunk + c reduces samples [c EV_CHUNK, min(N, (c + 1) EV_CHUNK)) of utterance b
@@ -77,14 +88,17 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_moments(EvalSepArgs a) {
   const float* t0 = a.tgt + (long long)b * 2 * a.tgt_ld + off;
   const float* t1 = t0 + a.tgt_ld;
   const float* m = a.mix ? a.mix + (long long)b * a.mix_ld + off : nullptr;
+  // the rows' first samples (sample 0 of the utterance, whatever the chunk); a missing mixture is a row of zeros
+  const double piv[5] = {(double)e0[-off], (double)e1[-off], (double)t0[-off], (double)t1[-off],
+                         m ? (double)m[-off] : 0.0};
   double s[EV_MOM];
 #pragma unroll
   for (int k = 0; k < EV_MOM; ++k) s[k] = 0.0;
   const uintptr_t bits = reinterpret_cast<uintptr_t>(e0) | reinterpret_cast<uintptr_t>(e1) |
                          reinterpret_cast<uintptr_t>(t0) | reinterpret_cast<uintptr_t>(t1) |
                          reinterpret_cast<uintptr_t>(m);
-  if ((bits & 15) == 0) ev_chunk<true>(e0, e1, t0, t1, m, len, s);
-  else ev_chunk<false>(e0, e1, t0, t1, m, len, s);
+  if ((bits & 15) == 0) ev_chunk<true>(e0, e1, t0, t1, m, len, piv, s);
+  else ev_chunk<false>(e0, e1, t0, t1, m, len, piv, s);
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
 #pragma unroll
   for (int k = 0; k < EV_MOM; ++k) {
@@ -99,7 +113,13 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_moments(EvalSepArgs a) {
   }
 }
 
-// <x, y> of the zero-mean rows from the raw moments
+// <x, y> of the rows themselves from the moments of x - cx and y - cy. One expression for <p,p>, <t,t> and <p,t>:
+// identical rows keep the three equal to the bit.
+__device__ __forceinline__ double ev_raw(double xy, double sx, double sy, double cx, double cy, double Nd) {
+  return fma(cx, sy, fma(cy, sx, fma(Nd * cx, cy, xy)));
+}
+
+// <x, y> of the zero-mean rows from the moments (of the shifted rows: the shift does not change it)
 __device__ __forceinline__ double ev_cen(double xy, double sx, double sy, double Nd, int zero_mean) {
   return zero_mean ? xy - sx * sy / Nd : xy;
 }
@@ -147,6 +167,14 @@ constexpr int EVF_BATCH = 16;  // chunk partials loaded before they are added (t
 // one number each (job below) from moments fetched from the lanes that hold them, and lane 0 chooses and stores.
 __global__ __launch_bounds__(64) void k_eval_finish(EvalSepArgs a) {
   const int b = blockIdx.x, l = threadIdx.x;
+  // zero_mean = 0 takes the shift of k_eval_moments out again: lane r < 5 fetches the first sample of row r (issued
+  // ahead of the partials; with zero_mean nothing needs it)
+  double piv = 0.0;
+  if (!a.zero_mean) {
+    if (l < 2) piv = (double)a.est[((long long)b * 2 + l) * a.est_ld];
+    else if (l < 4) piv = (double)a.tgt[((long long)b * 2 + l - 2) * a.tgt_ld];
+    else if (l == 4 && a.mix) piv = (double)a.mix[(long long)b * a.mix_ld];
+  }
   double v = 0.0;
   if (l < EV_MOM) {
     const double* p = a.partial + (long long)b * a.nchunk * EV_MOM + l;
@@ -169,9 +197,15 @@ __global__ __launch_bounds__(64) void k_eval_finish(EvalSepArgs a) {
   else { kind = job < 14 ? EVK_SI : EVK_SNR; row = 4; t = job & 1; }
   const int zm = job < 4 ? a.zero_mean : 1;
   const double Nd = (double)a.N;
-  const double sp = __shfl(v, EVM_S + row), qp = __shfl(v, EVM_Q + row);
-  const double st = __shfl(v, EVM_S + 2 + t), qt = __shfl(v, EVM_Q + 2 + t);
-  const double xy = __shfl(v, row == 4 ? EVM_MT + t : EVM_ET + 2 * row + t);
+  const double sp = __shfl(v, EVM_S + row), st = __shfl(v, EVM_S + 2 + t);
+  double qp = __shfl(v, EVM_Q + row), qt = __shfl(v, EVM_Q + 2 + t);
+  double xy = __shfl(v, row == 4 ? EVM_MT + t : EVM_ET + 2 * row + t);
+  const double cp = __shfl(piv, row), ct = __shfl(piv, 2 + t);
+  if (!zm) {
+    qp = ev_raw(qp, sp, sp, cp, cp, Nd);
+    qt = ev_raw(qt, st, st, ct, ct, Nd);
+    xy = ev_raw(xy, sp, st, cp, ct, Nd);
+  }
   const float r = (float)ev_score(kind, ev_energy(qp, sp, Nd, zm), ev_energy(qt, st, Nd, zm), ev_cen(xy, sp, st, Nd, zm),
                                   a.take_log, a.eps);
   float s[16];

@@ -3,46 +3,88 @@
 //   p = P[pidx[r]], t = Tg[tidx[r]] (rows of N samples; identity indices when null), optional zero mean,
 //   alpha = (<p,t> + eps) / (<t,t> + eps), ts = alpha t, e = ts - p,
 //   si_sdr = 10 log10((<ts,ts> + eps) / (<e,e> + eps)),  eps = float32 machine epsilon.
-// One workgroup per pair streams both rows once (float4 loads) and accumulates the five moments
-// {sum p, sum t, sum p^2, sum t^2, sum p t} in double; the zero-mean and scaled terms follow in closed
-// form: <p',t'> = <p,t> - N mp mt, <t',t'> = <t,t> - N mt^2, <e,e> = alpha^2 <t',t'> - 2 alpha <p',t'> + <p',p'>.
-// Fixed-order reductions: bitwise reproducible. HBM-bound (8 N bytes per pair).
+// One workgroup per pair streams both rows once and accumulates five moments in double; the zero-mean and scaled
+// terms follow in closed form: <p',t'> = <p,t> - N mp mt, <t',t'> = <t,t> - N mt^2,
+// <e,e> = alpha^2 <t',t'> - 2 alpha <p',t'> + <p',p'>.
+//
+// Conditioning. The closed form loses (mean^2 / variance) (signal / residual) of the moments' precision: taken on
+// the raw rows, a DC of 100 standard deviations at a 71 .. 78 dB residual moved the result by 3.1e-3 dB at N = 32 000
+// and by 0.14 dB at N = 2 000 000 (1000 standard deviations: 0.35 dB and 5.8 dB; measured), as much as or more than
+// the float32 reference it replaces. So with zero_mean the moments are those of p - p[0] and t - t[0]: the centred moments do not depend on
+// the shift, the subtraction of two floats is exact in double, and a row's own first sample leaves a mean of the
+// order of its standard deviation. Without zero_mean nothing is shifted (the raw moments are what the formula
+// asks for; its error stays below 1e-5 dB up to 80 dB). A thread adds 16 samples' terms on their own before they
+// join its running sum: squares of shifted floats share their low bits, and a running sum of thousands of them
+// rounds with a bias (2e-4 dB at N = 2 000 000, by emulation) that sums of 16 do not have. Measured table: DESIGN.md section 12,
+// tests/test_gpu_score_regimes.py.
+//
+// Fixed-order reductions: bitwise reproducible, and independent of the rows' alignment (the float4 and the scalar
+// path give each thread the same samples in the same order). HBM-bound (8 N bytes per pair).
 #include "device_common.h"
 
 namespace sepvad {
 
 constexpr int SD_THREADS = 256;
 
-// The five double moments of pair r; true on thread 0 only, which then holds them in m.
+// four consecutive samples 4 q .. 4 q + 3 of a row
+template <bool VEC>
+__device__ __forceinline__ void sd_load4(const float* p, long long q, float (&v)[4]) {
+  if (VEC) {
+    const float4 f = reinterpret_cast<const float4*>(p)[q];
+    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = p[4 * q + k];
+  }
+}
+
+// explicit fma: the same rounding in both paths whatever the compiler contracts
+__device__ __forceinline__ void sd_acc(double (&s)[5], float pf, float tf, double cp, double ct) {
+  const double x = (double)pf - cp, y = (double)tf - ct;
+  s[0] += x; s[1] += y;
+  s[2] = fma(x, x, s[2]); s[3] = fma(y, y, s[3]); s[4] = fma(x, y, s[4]);
+}
+
+// Thread q takes the float4 groups q, q + 256, ... of the row, four at a time into sums of their own.
+template <bool VEC>
+__device__ __forceinline__ void sd_row(const float* p, const float* t, long long N, double cp, double ct,
+                                       double (&s)[5]) {
+  const long long n4 = N / 4;
+  for (long long q0 = threadIdx.x; q0 < n4; q0 += 4 * SD_THREADS) {
+    float pa[4][4], ta[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long q = q0 + u * SD_THREADS;
+      if (q < n4) { sd_load4<VEC>(p, q, pa[u]); sd_load4<VEC>(t, q, ta[u]); }
+    }
+    double c[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (q0 + u * SD_THREADS < n4) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sd_acc(c, pa[u][k], ta[u][k], cp, ct);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) s[k] += c[k];
+  }
+  const long long i = n4 * 4 + threadIdx.x;  // the last N % 4 samples: one each for threads 0 .. 2
+  if (i < N) sd_acc(s, p[i], t[i], cp, ct);
+}
+
+// The five double moments {sum x, sum y, <x,x>, <y,y>, <x,y>} of pair r, x = p - p[0] and y = t - t[0] with
+// zero_mean, the rows themselves without; true on thread 0 only, which then holds them in m.
 __device__ __forceinline__ bool pair_moments(const SiSdrArgs& a, double (&m)[5]) {
   __shared__ double red[5 * 16];
   const int r = blockIdx.x;
   const long long pr = a.pidx ? a.pidx[r] : r, tr = a.tidx ? a.tidx[r] : r;
   const float* p = a.P + pr * a.p_ld;
   const float* t = a.Tg + tr * a.t_ld;
-  const long long N = a.N;
+  const double cp = a.zero_mean ? (double)p[0] : 0.0, ct = a.zero_mean ? (double)t[0] : 0.0;
   double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(t)) & 15) == 0;
-  long long n0 = 0;
-  if (vec) {
-    const long long n4 = N / 4;
-    const float4* p4 = reinterpret_cast<const float4*>(p);
-    const float4* t4 = reinterpret_cast<const float4*>(t);
-    for (long long i = threadIdx.x; i < n4; i += SD_THREADS) {
-      const float4 a4 = p4[i], b4 = t4[i];
-      const float pa[4] = {a4.x, a4.y, a4.z, a4.w}, ta[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const double x = pa[k], y = ta[k];
-        s[0] += x; s[1] += y; s[2] += x * x; s[3] += y * y; s[4] += x * y;
-      }
-    }
-    n0 = n4 * 4;
-  }
-  for (long long i = n0 + threadIdx.x; i < N; i += SD_THREADS) {
-    const double x = p[i], y = t[i];
-    s[0] += x; s[1] += y; s[2] += x * x; s[3] += y * y; s[4] += x * y;
-  }
+  if (vec) sd_row<true>(p, t, a.N, cp, ct, s);
+  else sd_row<false>(p, t, a.N, cp, ct, s);
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
