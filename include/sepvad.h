@@ -399,6 +399,50 @@ int32_t sepvad_eval_vad(const float* vad, float* labels, int32_t fix_labels, con
                         int32_t B, int32_t T, float* bce_rows, float* bce_mean, float* pw_ce, int32_t* conf,
                         int64_t* simple, int32_t* conf_simple, void* stream);
 
+/* ---- streaming evaluation with known targets (model/online_class_known_targets.py:85-154) --------
+ * The window loop of calc_online (:101-123) for the windows of one sepvad_forward_windows chunk in a fixed number of
+ * launches (csrc/stream_eval.hip): each window's PIT against its target window
+ * (criterion_separation, :106: PITLossWrapper(PairwiseNegSDR(sdr_type, zero_mean, take_log, eps), "pw_mtx"), with the
+ * bits of sepvad_eval_separation on that window and target slice), the similarity PIT of the window's overlap against
+ * the signal stitched so far (:108-117), reorder_source_mse and update_online_signal (:118-119, :29-38).
+ * mode selects the similarity criterion (test.py:96-106). */
+enum {
+  SEPVAD_SE_NONE = 0,   /* criterion_similarity None: every window is appended under its target permutation */
+  SEPVAD_SE_L1 = 1,     /* PITLossWrapper(nn.L1Loss(), "pw_pt"): one scalar per pair over batch and samples, so the
+                           permutation is shared by the batch (as sepvad_pit_l1) */
+  SEPVAD_SE_SISDR = 2   /* PITLossWrapper(calc_sisdr_loss, "pw_pt") (model/combined_loss.py:16-60): per-row losses, a
+                           permutation per row */
+};
+
+/* HOST query: bytes of device scratch one sepvad_stream_eval call needs for n windows of B streams. SEPVAD_E_ARG for B
+ * outside 1..65535, n < 1, H < 1, H > W, an unknown mode, 2 H > W or more than 4096 hops per window in a similarity
+ * mode, or a chunk above 2^31 - 1 workgroups. Monotone in n. */
+int64_t sepvad_stream_eval_scratch_bytes(int32_t B, int32_t n, int64_t W, int64_t H, int32_t mode);
+
+/* sep: the separations of windows k0 .. k0 + n - 1 of K, window-major [n][B][2][sep_ld] with W samples per row
+ * (sepvad_forward_windows' layout); window k starts at sample k H of its stream. tgt: [B][2][tgt_ld], the padded
+ * targets, read in place at + k H (tgt_ld >= (K - 1) H + W). The caller owns every buffer and keeps the persistent
+ * ones between the chunks of one signal (the entry is stateless, like the streaming entries above):
+ *   raw    [B][2][raw_ld]     every window's own last hop at k H, un-permuted (raw_ld >= K H); window k is compared
+ *                             with raw[k H - L_k, k H), L_k = min(k H, W - H), each hop under the permutation of the
+ *                             window it came from; window 0 with its own last hop (the reference's seed, :109-111)
+ *   perm   [K][B][2] int64    the permutation each window is appended under (perm[k][b][t] = the estimate that
+ *                             becomes speaker t): the target permutation with SEPVAD_SE_NONE, else the similarity one
+ *   online [B][2][online_ld]  the stitched signal, online[b][t][k H + i] = sep[k][b][perm[k][b][t]][W - H + i]
+ * and the per-window outputs pw_tgt [K][B][2][2], loss_tgt [K][B], perm_tgt [K][B][2] int64 (pw, min_loss and perm of
+ * sepvad_eval_separation; perm_tgt is nullable with SEPVAD_SE_NONE, where perm receives it) and pw_sim [K][G][2][2]
+ * (the similarity PIT's pairwise table, estimate i against stitched speaker j; G = B with SEPVAD_SE_SISDR, 1 with
+ * SEPVAD_SE_L1; nullable, unused with SEPVAD_SE_NONE). Chunks must arrive in window order; any split into chunks
+ * gives the bits of one call. Ties keep the identity. Sums in double in a fixed order: bitwise reproducible.
+ * scratch: 8-byte aligned device memory of scratch_bytes >= the query above.
+ * SEPVAD_E_ARG (nothing launched) for a null pointer (the nullable ones excepted), what the query refuses, k0 < 0,
+ * k0 + n > K, a row stride below its row's length, an unknown sdr_type, a short or misaligned scratch. */
+int32_t sepvad_stream_eval(const float* sep, int64_t sep_ld, int32_t n, int32_t k0, int32_t K, int32_t B, int64_t W,
+                           int64_t H, const float* tgt, int64_t tgt_ld, int32_t mode, int32_t sdr_type,
+                           int32_t zero_mean, int32_t take_log, double eps, float* raw, int64_t raw_ld, float* online,
+                           int64_t online_ld, int64_t* perm, int64_t* perm_tgt, float* pw_tgt, float* loss_tgt,
+                           float* pw_sim, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- synthetic reverberant mixtures (BASELINE cfg 4): image-method room impulse responses --------
  * Replaces pyrirgen.generateRir / gen_rir (create_data/rirgen.cpp:115-351, create_data/pyrirgen.pyx)
  * as create_data/create_simulation_data.py:284-289 calls it. HOST function, double precision:

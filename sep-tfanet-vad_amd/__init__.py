@@ -10,9 +10,10 @@ from .config import (CONFIG_WITH_VAD, CONFIG_WITHOUT_VAD, DEFAULTS, INFERENCE_KW
 from .model import SeparationModel
 from .live import LiveSeparator
 from .online import OnlineSaving
+from .online_known import OnlineSaving as OnlineSavingKnownTargets
 from .pit import PITLossWrapper, reorder_source_mse
 
 __all__ = [
-    "SeparationModel", "OnlineSaving", "LiveSeparator", "PITLossWrapper", "reorder_source_mse", "CONFIG_WITH_VAD", "CONFIG_WITHOUT_VAD", "DEFAULTS",
+    "SeparationModel", "OnlineSaving", "OnlineSavingKnownTargets", "LiveSeparator", "PITLossWrapper", "reorder_source_mse", "CONFIG_WITH_VAD", "CONFIG_WITHOUT_VAD", "DEFAULTS",
     "INFERENCE_KW_DEFAULTS", "param_spec", "frames",
 ]

@@ -509,6 +509,73 @@ int32_t sepvad_eval_separation(const float* est, int64_t est_ld, const float* tg
   HIPRET(launch_eval_separation(a, (hipStream_t)stream));
 }
 
+// calc_online's window loop with known targets (model/online_class_known_targets.py:101-123): csrc/stream_eval.hip.
+// Scratch (doubles): segment sums [n][S][B][SE_NV] | their batch sums [n][S][4] | launch_pit_l1's scratch | the target
+// moments' partials [n B][nchunk][EV_MOM] | eval.hip's row values [n B][EV_ROWVALS]
+namespace {
+struct SeLayout { int64_t seg, bsum, pit0, partial, rowvals, total; int S, nchunk; };
+const char* se_layout(int32_t B, int32_t n, int64_t W, int64_t H, int32_t mode, SeLayout& L) {
+  if (B < 1 || B > 65535 || n < 1) return "need 1 <= B <= 65535 and n >= 1";
+  if (H < 1 || H > W || W > INT32_MAX) return "need 1 <= H <= W < 2^31";
+  if (mode < SEPVAD_SE_NONE || mode > SEPVAD_SE_SISDR) return "unknown mode";
+  const bool sim = mode != SEPVAD_SE_NONE;
+  if (sim && 2 * H > W) return "a similarity mode needs 2 H <= W (the reference's slices stop matching beyond)";
+  L.S = sim ? se_segments(W, H) : 0;
+  if (L.S > SE_MAX_SEG) return "a similarity mode takes at most 4096 hops per window";
+  L.nchunk = (int)((W + EV_CHUNK - 1) / EV_CHUNK);
+  const int64_t nu = (int64_t)n * B;
+  if (nu * ((int64_t)L.S + L.nchunk) > INT32_MAX) return "the chunk exceeds 2^31 - 1 workgroups (fewer windows per call)";
+  L.seg = 0;
+  L.bsum = L.seg + nu * L.S * SE_NV;
+  L.pit0 = L.bsum + (mode == SEPVAD_SE_L1 ? (int64_t)n * L.S * 4 : 0);
+  L.partial = L.pit0 + (mode == SEPVAD_SE_L1 ? SEPVAD_PIT_SCRATCH_BYTES / (int64_t)sizeof(double) : 0);
+  L.rowvals = L.partial + nu * L.nchunk * EV_MOM;
+  L.total = (L.rowvals + nu * EV_ROWVALS) * (int64_t)sizeof(double);
+  return nullptr;
+}
+}  // namespace
+
+int64_t sepvad_stream_eval_scratch_bytes(int32_t B, int32_t n, int64_t W, int64_t H, int32_t mode) {
+  SeLayout L{};
+  if (const char* why = se_layout(B, n, W, H, mode, L))
+    return fail(SEPVAD_E_ARG, std::string("sepvad_stream_eval_scratch_bytes: ") + why);
+  return L.total;
+}
+
+int32_t sepvad_stream_eval(const float* sep, int64_t sep_ld, int32_t n, int32_t k0, int32_t K, int32_t B, int64_t W,
+                           int64_t H, const float* tgt, int64_t tgt_ld, int32_t mode, int32_t sdr_type,
+                           int32_t zero_mean, int32_t take_log, double eps, float* raw, int64_t raw_ld, float* online,
+                           int64_t online_ld, int64_t* perm, int64_t* perm_tgt, float* pw_tgt, float* loss_tgt,
+                           float* pw_sim, void* scratch, int64_t scratch_bytes, void* stream) {
+  SeLayout L{};
+  if (const char* why = se_layout(B, n, W, H, mode, L)) return fail(SEPVAD_E_ARG, std::string("sepvad_stream_eval: ") + why);
+  if (!sep || !tgt || !raw || !online || !perm || !pw_tgt || !loss_tgt || !scratch || (mode != SEPVAD_SE_NONE && !perm_tgt))
+    return fail(SEPVAD_E_ARG, "sepvad_stream_eval: null pointer");
+  if (k0 < 0 || K < 1 || (int64_t)k0 + n > K) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: need 0 <= k0 and k0 + n <= K");
+  if (sep_ld < W || tgt_ld < (int64_t)(K - 1) * H + W || raw_ld < (int64_t)K * H || online_ld < (int64_t)K * H)
+    return fail(SEPVAD_E_ARG, "sepvad_stream_eval: row strides must cover W (sep), (K - 1) H + W (tgt) and K H (raw, online)");
+  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: unknown sdr_type");
+  if (scratch_bytes < L.total) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: scratch too small (sepvad_stream_eval_scratch_bytes)");
+  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: scratch must be 8-byte aligned");
+  StreamEvalArgs a{};
+  a.B = B; a.n = n; a.k0 = k0; a.K = K; a.mode = mode; a.W = W; a.H = H; a.S = L.S;
+  a.sep = sep; a.sep_ld = sep_ld; a.raw = raw; a.raw_ld = raw_ld; a.online = online; a.on_ld = online_ld;
+  a.perm = (long long*)perm; a.pw_sim = pw_sim;
+  double* sc = (double*)scratch;
+  a.seg = sc + L.seg; a.bsum = sc + L.bsum;
+  if (mode == SEPVAD_SE_L1 && k0 == 0)  // window 0's seed comparison: its second-last hop against its own last hop
+    a.pit0 = pit_args(sep + (W - 2 * H), sep_ld, raw, raw_ld, B, H, pit_batch_blocks(B, H), sc + L.pit0, perm, nullptr, pw_sim);
+  const int64_t w0 = (int64_t)k0 * B;  // the per-window outputs of this chunk start at window k0
+  EvalSepArgs& e = a.ev;
+  e.est = sep; e.est_ld = sep_ld; e.tgt = tgt + (int64_t)k0 * H; e.tgt_ld = tgt_ld;
+  e.B = n * B; e.N = W; e.nchunk = L.nchunk;
+  e.sdr_type = sdr_type; e.zero_mean = zero_mean != 0; e.take_log = take_log != 0; e.eps = eps;
+  e.partial = sc + L.partial; e.rowvals = sc + L.rowvals;
+  e.pw = pw_tgt + w0 * 4; e.min_loss = loss_tgt + w0;
+  e.perm = (long long*)(mode == SEPVAD_SE_NONE ? perm : perm_tgt) + w0 * 2;
+  HIPRET(launch_stream_eval(a, (hipStream_t)stream));
+}
+
 // BinaryCrossEntropyLoss_Mean (model/combined_loss.py:120-138), pit_CE_vad's pairwise table (model/metric.py:264),
 // the confusion counts of test.py:164,172 and calc_vad (Our_utils/utils_test.py:67-73): csrc/eval.hip
 int32_t sepvad_eval_vad(const float* vad, float* labels, int32_t fix_labels, const int64_t* perm, const float* masks,

@@ -112,6 +112,21 @@ __device__ __forceinline__ void block_reduce_store(float (&v)[NV], float* lds, d
   }
 }
 
+// dst[0, n) = src[0, n) by threads tid, tid + nth, ...: float4 where both pointers are 16-byte aligned (the last
+// n % 4 scalar), scalar otherwise (stream.hip, stream_eval.hip)
+__device__ __forceinline__ void copy_run(float* dst, const float* src, long long n, long long tid, long long nth) {
+  if (n <= 0) return;
+  if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0) {
+    const long long n4 = n >> 2;
+    const float4* s4 = reinterpret_cast<const float4*>(src);
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    for (long long i = tid; i < n4; i += nth) d4[i] = s4[i];
+    for (long long i = (n4 << 2) + tid; i < n; i += nth) dst[i] = src[i];
+  } else {
+    for (long long i = tid; i < n; i += nth) dst[i] = src[i];
+  }
+}
+
 // x' for one element: o = X value, r = X2 value, g = a_f[k] * a_t[t] (1 when attention is off).
 template <int MODE>
 __device__ __forceinline__ float resid_apply(float o, float r, float g, int k, const float* c0, const float* c1,

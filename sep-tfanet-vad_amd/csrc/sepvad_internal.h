@@ -362,6 +362,26 @@ struct EvalVadArgs {
 };
 hipError_t launch_eval_vad(const EvalVadArgs& a, hipStream_t s);
 
+// streaming evaluation with known targets (stream_eval.hip): one chunk of n windows (first window k0 of K) of B streams
+constexpr int SE_NV = 12;          // doubles per (window, segment, stream): SE_* in stream_eval.hip
+constexpr int SE_MAX_SEG = 4096;   // hop segments of one window's overlap, ceil((W - H) / H), kept in LDS by the chain
+inline int se_segments(long long W, long long H) { return (int)((W - H + H - 1) / H); }
+struct StreamEvalArgs {
+  int B, n, k0, K, mode;             // mode: SEPVAD_SE_*
+  long long W, H; int S;             // window, hop, segments per window
+  const float* sep; long long sep_ld;   // [n][B][2][sep_ld] window-major separations of the chunk
+  float* raw; long long raw_ld;      // [B][2][raw_ld] every window's own last hop, window k at k H
+  float* online; long long on_ld;    // [B][2][on_ld] the stitched signal
+  long long* perm;                   // [K][B][2] the permutation each window is appended under
+  float* pw_sim;                     // [K][G][2][2] similarity tables, G = B (SEPVAD_SE_SISDR) or 1 (SEPVAD_SE_L1)
+  double* seg;                       // [n][S][B][SE_NV] scratch
+  double* bsum;                      // [n][S][4] scratch (SEPVAD_SE_L1: the segment sums over the batch)
+  PitArgs pit0;                      // SEPVAD_SE_L1 and k0 == 0: window 0's seed comparison as launch_pit_l1 (nblk 0: off)
+  EvalSepArgs ev;                    // the chunk's n B window-utterances against their target windows: tgt is the
+                                     // stream's target row at window k0 (window kl at + kl H), outputs at window k0
+};
+hipError_t launch_stream_eval(const StreamEvalArgs& a, hipStream_t s);
+
 // ---- fused persistent TCN (tcn_kernel.h; dispatch fused.hip, instantiations fused_inst.hip) ----
 constexpr int FR = 32;          // frames per workgroup
 #ifndef SEPVAD_FG_MAX

@@ -200,21 +200,7 @@ hipError_t launch_stream_append(const AppendArgs& a, hipStream_t s) {
 }
 
 // ---- live sessions: mirrored rings and the per-window stitch --------------------------------------------------------
-// dst[0, n) = src[0, n) by the whole block: float4 where both pointers are 16-byte aligned (the last n % 4 scalar),
-// scalar otherwise
-__device__ __forceinline__ void copy_run(float* dst, const float* src, long long n, long long tid, long long nth) {
-  if (n <= 0) return;
-  if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0) {
-    const long long n4 = n >> 2;
-    const float4* s4 = reinterpret_cast<const float4*>(src);
-    float4* d4 = reinterpret_cast<float4*>(dst);
-    for (long long i = tid; i < n4; i += nth) d4[i] = s4[i];
-    for (long long i = (n4 << 2) + tid; i < n; i += nth) dst[i] = src[i];
-  } else {
-    for (long long i = tid; i < n; i += nth) dst[i] = src[i];
-  }
-}
-
+// (copy_run: device_common.h)
 // n samples of src into the mirrored ring row [2R] at pos: the run up to the wrap and the run after it, each twice
 __device__ __forceinline__ void ring_store(float* ring, long long R, long long pos, const float* src, long long n,
                                            long long tid, long long nth) {

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "sepvad_resample_filter", "sepvad_resample", "sepvad_normalize", "sepvad_si_sdr", "sepvad_vad_accuracy",
     "sepvad_snr", "sepvad_stoi_filter", "sepvad_stoi_scratch_bytes", "sepvad_stoi",
     "sepvad_eval_scratch_bytes", "sepvad_eval_separation", "sepvad_eval_vad",
+    "sepvad_stream_eval_scratch_bytes", "sepvad_stream_eval",
     "sepvad_rir_generate",
     "sepvad_rir_jobs_prepare", "sepvad_rir_scratch_bytes", "sepvad_rir_generate_device", "sepvad_fir_convolve",
     "sepvad_scene_mix", "sepvad_scene_targets", "sepvad_vad_frame_labels",
@@ -197,6 +198,11 @@ def load_library(path: str = LIB_PATH):
                                            P, P, P, P, P, P]
     lib.sepvad_eval_vad.restype = i32
     lib.sepvad_eval_vad.argtypes = [P, P, i32, P, P, i32, i32, P, P, P, P, P, P, P]
+    lib.sepvad_stream_eval_scratch_bytes.restype = i64
+    lib.sepvad_stream_eval_scratch_bytes.argtypes = [i32, i32, i64, i64, i32]
+    lib.sepvad_stream_eval.restype = i32
+    lib.sepvad_stream_eval.argtypes = [P, i64, i32, i32, i32, i32, i64, i64, P, i64, i32, i32, i32, i32, ctypes.c_double,
+                                       P, i64, P, i64, P, P, P, P, P, P, i64, P]
     dptr = ctypes.POINTER(ctypes.c_double)
     lib.sepvad_rir_generate.restype = i32
     lib.sepvad_rir_generate.argtypes = [ctypes.c_double, ctypes.c_double, dptr, i32, dptr, dptr, dptr, i32, dptr,

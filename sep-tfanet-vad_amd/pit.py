@@ -131,6 +131,28 @@ def pit_l1_sharded(est: torch.Tensor, ref: torch.Tensor, total_rows: int, group=
     return loss, perm, pw
 
 
+def pit_sisdr_rows(est: torch.Tensor, ref: torch.Tensor):
+    """``PITLossWrapper(calc_sisdr_loss, "pw_pt")`` for two sources (``model/pit_wrapper.py:149-177,287-312`` over
+    ``model/combined_loss.py:16-60``): ``calc_sisdr_loss`` returns one loss per row, so the pairwise table and the
+    permutation are per row. (mean of the rows' min losses [scalar], batch_indices [B, 2] int64, pairwise [B, 2, 2]
+    with estimate i against target j at [b, i, j]) on the device: the four pairs of every row are one ``sepvad_si_sdr``
+    call through its index arrays, negated; float32 adds and torch.min's first minimum choose per row."""
+    from .metrics import _si_sdr_pairs
+    if est.device.type != "cuda" or ref.device != est.device:
+        raise RuntimeError("pit_sisdr_rows: est and ref must be on the same ROCm device")
+    if est.shape != ref.shape or est.dim() != 3 or est.shape[1] != 2:
+        raise ValueError(f"pit_sisdr_rows: expected two [B, 2, L] tensors, got {tuple(est.shape)} and {tuple(ref.shape)}")
+    B, _, L = est.shape
+    P = est.to(torch.float32).reshape(2 * B, L).contiguous()
+    Tg = ref.to(torch.float32).reshape(2 * B, L).contiguous()
+    r = torch.arange(4 * B, device=est.device, dtype=torch.int32)  # pair r = 4 b + 2 i + j
+    pw = -_si_sdr_pairs(P, Tg, (r >> 2) * 2 + ((r >> 1) & 1), (r >> 2) * 2 + (r & 1), True).reshape(B, 2, 2)
+    loss_id, loss_sw = (pw[:, 0, 0] + pw[:, 1, 1]) / 2, (pw[:, 1, 0] + pw[:, 0, 1]) / 2
+    swap = (loss_sw < loss_id).to(torch.int64)
+    perm = torch.stack([swap, 1 - swap], dim=1)
+    return torch.minimum(loss_id, loss_sw).mean(), perm, pw
+
+
 def stream_append(src: torch.Tensor, s0: int, H: int, perm, dst: torch.Tensor, d0: int):
     """dst[b, i, d0:d0+H] = src[b, perm[b, i], s0:s0+H] (perm None = identity), on the device."""
     lib = _native.load_library()
@@ -162,6 +184,8 @@ class PITLossWrapper(nn.Module):
 
     * ``loss_func`` an ``nn.L1Loss`` with reduction "mean", ``pit_from="pw_pt"`` — the criterion the streaming
       wrapper is built with;
+    * ``loss_func`` ``calc_sisdr_loss`` (``metrics`` / ``combined_loss``), ``pit_from="pw_pt"`` — ``si_sdr_loss_similarity``
+      of ``test.py:102-105``: per-row losses, a permutation per row (``pit_sisdr_rows``);
     * ``loss_func`` a ``sdr.PairwiseNegSDR``, ``pit_from="pw_mtx"`` — ``loss_separation`` of both shipped configs
       (``test.py:49-56``): a permutation per utterance (``sepvad_eval_separation``);
     * ``loss_func`` a ``combined_loss.BinaryCrossEntropyLoss_Mean``, ``pit_from="pw_pt"`` — ``loss_vad`` and
@@ -188,8 +212,12 @@ class PITLossWrapper(nn.Module):
     def _criterion_forward(self, est_targets, targets, n_src, kwargs):
         """(mean loss, batch_indices [B, 2] int64) of the two evaluation criteria of test.py:49-61."""
         from .evaluate import BinaryCrossEntropyLoss_Mean, eval_vad
+        from .metrics import calc_sisdr_loss
         from .sdr import PairwiseNegSDR
         plain = self.perm_reduce is None or self.perm_reduce is False
+        if plain and not kwargs and n_src == 2 and self.pit_from == "pw_pt" and self.loss_func is calc_sisdr_loss:
+            mean_loss, batch_indices, _ = pit_sisdr_rows(est_targets, targets)
+            return mean_loss, batch_indices
         if plain and not kwargs and self.pit_from == "pw_mtx" and isinstance(self.loss_func, PairwiseNegSDR):
             r = self.loss_func.evaluate(est_targets, targets)  # its TypeError / NotImplementedError on bad shapes
             return r["means"][0], r["perm"]
@@ -203,6 +231,7 @@ class PITLossWrapper(nn.Module):
             ident = torch.arange(2, device=pw.device)
             return torch.minimum(loss_id, loss_sw), (ident ^ swap).expand(targets.shape[0], 2).contiguous()
         raise NotImplementedError("native PIT: built for 2 sources and PITLossWrapper(nn.L1Loss(), 'pw_pt'), "
+                                  "PITLossWrapper(calc_sisdr_loss, 'pw_pt'), "
                                   "PITLossWrapper(sdr.PairwiseNegSDR(...), 'pw_mtx') or "
                                   "PITLossWrapper(combined_loss.BinaryCrossEntropyLoss_Mean(), 'pw_pt'), without "
                                   "perm_reduce or extra arguments")
