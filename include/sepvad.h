@@ -399,6 +399,42 @@ int32_t sepvad_eval_vad(const float* vad, float* labels, int32_t fix_labels, con
                         int32_t B, int32_t T, float* bce_rows, float* bce_mean, float* pw_ce, int32_t* conf,
                         int64_t* simple, int32_t* conf_simple, void* stream);
 
+/* ---- the training criterion's backward (trainer/trainer.py:57-63: criterion(...) then loss.backward()) ----------
+ * The gradients of CombinedLoss (model/combined_loss.py:93-138) over PITLossWrapper(PairwiseNegSDR(...), "pw_mtx")
+ * (model/sdr.py:48-86) and the weighted BCE with respect to the separated signals and the VAD track. The forward is
+ * sepvad_eval_separation and sepvad_eval_vad as they are; the gradient of an estimate row is a combination of that row
+ * and of its paired target row, both centred when zero_mean, whose coefficients follow from the forward's moments
+ * (csrc/criterion.hip). */
+enum { SEPVAD_CRIT_COEF = 6 };  /* doubles per estimate row in coef: c_t, c_n, a, mean of the estimate row, mean of the
+                                   paired target row (both 0 without zero_mean), index of the paired target */
+
+/* After sepvad_eval_separation(est, tgt, ..., B, N, sdr_type, zero_mean, take_log, eps, scratch, ..., perm, ...) on
+ * the same stream, with the same arguments and before anything else writes scratch: coef[b][i][SEPVAD_CRIT_COEF]
+ * (device, doubles) such that, for estimate row i of utterance b paired with target j (perm[b][j] = i),
+ *   d pw[b][i][j] / d est[b][i][n] = c_t t'[n] + c_n (e'[n] - a t'[n]),  e' = est[b][i] - mean e, t' = tgt[b][j] - mean t:
+ * the exact derivative of model/sdr.py:54-86 with its EPS placement (finite zeros on silence). coef is all a backward
+ * needs beside the rows: scratch may be overwritten afterwards. SEPVAD_E_ARG (nothing launched) for a null pointer,
+ * B < 1, B > 65535, N < 1, N > 2^40, a row stride below N, an unknown sdr_type, a short or misaligned scratch. */
+int32_t sepvad_criterion_coef(const float* est, int64_t est_ld, const float* tgt, int64_t tgt_ld, int32_t B, int64_t N,
+                              int32_t sdr_type, int32_t zero_mean, int32_t take_log, double eps, const void* scratch,
+                              int64_t scratch_bytes, const int64_t* perm, double* coef, void* stream);
+
+/* Replaces loss.backward() through the reference criterion (trainer/trainer.py:57-63; model/sdr.py:48-86 and
+ * model/combined_loss.py:93-138 under autograd). Two independent parts, either may be left out:
+ *   est != NULL: grad_est[b][i][n] = g_sep / (2 B) (c_t t'[n] + c_n (e'[n] - a t'[n])) from coef (above), for
+ *     est, tgt [B][2][ld] rows of N samples as sepvad_eval_separation takes them and grad_est [B][2][grad_ld];
+ *     evaluated in double from the float32 samples, rounded once;
+ *   vad != NULL: grad_vad[b][perm[b][s]][t] = g_vad / B  w (p - y) / max(p (1 - p), 1e-12f), p = vad[b][perm[b][s]][t],
+ *     y = labels[b][s][t] (2 counts as 1), w = 0.36 y + 0.64 (1 - y); contiguous [B][2][T]; perm nullable (identity).
+ * g_sep, g_vad: the upstream gradients of the two mean losses, one float32 each ON THE DEVICE (no host read). No
+ * atomics: bitwise reproducible, independent of the rows' alignment and strides, and B times the gradient of
+ * utterance b depends on its own rows only. SEPVAD_E_ARG (nothing launched) for B < 1, B > 65535, both parts left out,
+ * a part with a null pointer (perm excepted), N < 1, N > 2^40, a row stride below N or T < 1. */
+int32_t sepvad_criterion_backward(int32_t B, const float* est, int64_t est_ld, const float* tgt, int64_t tgt_ld,
+                                  int64_t N, const double* coef, const float* g_sep, float* grad_est, int64_t grad_ld,
+                                  const float* vad, const float* labels, const int64_t* perm, int32_t T,
+                                  const float* g_vad, float* grad_vad, void* stream);
+
 /* ---- streaming evaluation with known targets (model/online_class_known_targets.py:85-154) --------
  * The window loop of calc_online (:101-123) for the windows of one sepvad_forward_windows chunk in a fixed number of
  * launches (csrc/stream_eval.hip): each window's PIT against its target window

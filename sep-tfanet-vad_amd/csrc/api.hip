@@ -594,6 +594,50 @@ int32_t sepvad_eval_vad(const float* vad, float* labels, int32_t fix_labels, con
   HIPRET(launch_eval_vad(a, (hipStream_t)stream));
 }
 
+// the backward of the training criterion (trainer/trainer.py:57-63 over model/sdr.py:48-86 and
+// model/combined_loss.py:93-138): csrc/criterion.hip
+int32_t sepvad_criterion_coef(const float* est, int64_t est_ld, const float* tgt, int64_t tgt_ld, int32_t B, int64_t N,
+                              int32_t sdr_type, int32_t zero_mean, int32_t take_log, double eps, const void* scratch,
+                              int64_t scratch_bytes, const int64_t* perm, double* coef, void* stream) {
+  if (!est || !tgt || !scratch || !perm || !coef) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: null pointer");
+  if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40)) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: need 1 <= B <= 65535, 1 <= N <= 2^40");
+  if (est_ld < N || tgt_ld < N) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: row strides must be >= N");
+  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: unknown sdr_type");
+  if (scratch_bytes < eval_scratch(B, N)) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: scratch too small (sepvad_eval_scratch_bytes)");
+  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: scratch must be 8-byte aligned");
+  CritCoefArgs a{};
+  a.est = est; a.est_ld = est_ld; a.tgt = tgt; a.tgt_ld = tgt_ld;
+  a.B = B; a.N = N; a.nchunk = (int)eval_chunks(N);
+  a.sdr_type = sdr_type; a.zero_mean = zero_mean != 0; a.take_log = take_log != 0; a.eps = eps;
+  a.partial = (const double*)scratch; a.perm = (const long long*)perm; a.coef = coef;
+  HIPRET(launch_crit_coef(a, (hipStream_t)stream));
+}
+
+int32_t sepvad_criterion_backward(int32_t B, const float* est, int64_t est_ld, const float* tgt, int64_t tgt_ld,
+                                  int64_t N, const double* coef, const float* g_sep, float* grad_est, int64_t grad_ld,
+                                  const float* vad, const float* labels, const int64_t* perm, int32_t T,
+                                  const float* g_vad, float* grad_vad, void* stream) {
+  if (B < 1 || B > 65535) return fail(SEPVAD_E_ARG, "sepvad_criterion_backward: need 1 <= B <= 65535");
+  if (!est && !vad) return fail(SEPVAD_E_ARG, "sepvad_criterion_backward: neither a separation nor a VAD part");
+  CritGradArgs a{};
+  a.B = B;
+  if (est) {
+    if (!tgt || !coef || !g_sep || !grad_est) return fail(SEPVAD_E_ARG, "sepvad_criterion_backward: null pointer (separation part)");
+    if (N < 1 || N > (1LL << 40)) return fail(SEPVAD_E_ARG, "sepvad_criterion_backward: need 1 <= N <= 2^40");
+    if (est_ld < N || tgt_ld < N || grad_ld < N) return fail(SEPVAD_E_ARG, "sepvad_criterion_backward: row strides must be >= N");
+    const int64_t nchunk = (N + CG_CHUNK - 1) / CG_CHUNK;
+    if (B * nchunk > INT32_MAX) return fail(SEPVAD_E_ARG, "sepvad_criterion_backward: more than 2^31 - 1 workgroups (fewer utterances per call)");
+    a.est = est; a.est_ld = est_ld; a.tgt = tgt; a.tgt_ld = tgt_ld; a.N = N; a.nchunk = (int)nchunk;
+    a.coef = coef; a.g_sep = g_sep; a.grad_est = grad_est; a.grad_ld = grad_ld;
+  }
+  if (vad) {
+    if (!labels || !g_vad || !grad_vad) return fail(SEPVAD_E_ARG, "sepvad_criterion_backward: null pointer (VAD part)");
+    if (T < 1) return fail(SEPVAD_E_ARG, "sepvad_criterion_backward: need T >= 1");
+    a.vad = vad; a.labels = labels; a.perm = (const long long*)perm; a.T = T; a.g_vad = g_vad; a.grad_vad = grad_vad;
+  }
+  HIPRET(launch_crit_grad(a, (hipStream_t)stream));
+}
+
 int32_t sepvad_normalize(const float* x, int64_t n, float* y, void* scratch, void* stream) {
   if (!x || !y || !scratch || n < 1) return fail(SEPVAD_E_ARG, "sepvad_normalize: bad arguments");
   static_assert(NORM_MAX_BLOCKS * 2 * sizeof(float) <= SEPVAD_NORM_SCRATCH_BYTES, "scratch size");

@@ -362,6 +362,36 @@ struct EvalVadArgs {
 };
 hipError_t launch_eval_vad(const EvalVadArgs& a, hipStream_t s);
 
+// the training criterion's backward (criterion.hip): gradient coefficients from the moments launch_eval_separation
+// left in scratch, then the gradients of the separated signals and of the VAD track
+constexpr int CRIT_COEF = 6;    // doubles per estimate row: SEPVAD_CRIT_COEF (c_t, c_n, a, mean e, mean t, paired target)
+constexpr int CG_CHUNK = 1024;  // samples per workgroup of k_crit_grad_sep (a multiple of 4, as EV_CHUNK)
+struct CritCoefArgs {
+  const float* est; long long est_ld;   // [B][2][est_ld]: the rows the moments were taken of (their first samples)
+  const float* tgt; long long tgt_ld;
+  int B; long long N; int nchunk;       // nchunk = ceil(N / EV_CHUNK)
+  int sdr_type, zero_mean, take_log; double eps;
+  const double* partial;                // [B][nchunk][EV_MOM]
+  const long long* perm;                // [B][2]
+  double* coef;                         // [B][2][CRIT_COEF]
+};
+hipError_t launch_crit_coef(const CritCoefArgs& a, hipStream_t s);
+struct CritGradArgs {
+  int B;
+  const float* est; long long est_ld;   // null: no separation gradient
+  const float* tgt; long long tgt_ld;
+  long long N; int nchunk;              // nchunk = ceil(N / CG_CHUNK)
+  const double* coef;                   // [B][2][CRIT_COEF]
+  const float* g_sep;                   // [1] upstream gradient of the separation loss (device)
+  float* grad_est; long long grad_ld;   // [B][2][grad_ld]
+  const float* vad; const float* labels;   // [B][2][T]; vad null: no VAD gradient
+  const long long* perm;                // [B][2], nullable (identity)
+  int T;
+  const float* g_vad;                   // [1] upstream gradient of the VAD loss (device)
+  float* grad_vad;                      // [B][2][T]
+};
+hipError_t launch_crit_grad(const CritGradArgs& a, hipStream_t s);
+
 // streaming evaluation with known targets (stream_eval.hip): one chunk of n windows (first window k0 of K) of B streams
 constexpr int SE_NV = 12;          // doubles per (window, segment, stream): SE_* in stream_eval.hip
 constexpr int SE_MAX_SEG = 4096;   // hop segments of one window's overlap, ceil((W - H) / H), kept in LDS by the chain

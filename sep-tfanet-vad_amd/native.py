@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "sepvad_snr", "sepvad_stoi_filter", "sepvad_stoi_scratch_bytes", "sepvad_stoi",
     "sepvad_eval_scratch_bytes", "sepvad_eval_separation", "sepvad_eval_vad",
     "sepvad_stream_eval_scratch_bytes", "sepvad_stream_eval",
+    "sepvad_criterion_coef", "sepvad_criterion_backward",
     "sepvad_rir_generate",
     "sepvad_rir_jobs_prepare", "sepvad_rir_scratch_bytes", "sepvad_rir_generate_device", "sepvad_fir_convolve",
     "sepvad_scene_mix", "sepvad_scene_targets", "sepvad_vad_frame_labels",
@@ -203,6 +204,10 @@ def load_library(path: str = LIB_PATH):
     lib.sepvad_stream_eval.restype = i32
     lib.sepvad_stream_eval.argtypes = [P, i64, i32, i32, i32, i32, i64, i64, P, i64, i32, i32, i32, i32, ctypes.c_double,
                                        P, i64, P, i64, P, P, P, P, P, P, i64, P]
+    lib.sepvad_criterion_coef.restype = i32
+    lib.sepvad_criterion_coef.argtypes = [P, i64, P, i64, i32, i64, i32, i32, i32, ctypes.c_double, P, i64, P, P, P]
+    lib.sepvad_criterion_backward.restype = i32
+    lib.sepvad_criterion_backward.argtypes = [i32, P, i64, P, i64, i64, P, P, P, i64, P, P, P, i32, P, P, P]
     dptr = ctypes.POINTER(ctypes.c_double)
     lib.sepvad_rir_generate.restype = i32
     lib.sepvad_rir_generate.argtypes = [ctypes.c_double, ctypes.c_double, dptr, i32, dptr, dptr, dptr, i32, dptr,

@@ -1,0 +1,158 @@
+"""The training criterion without a GPU: the float64 restatement against the reference's own autograd
+(tests/golden/golden_train_criterion.npz, make_train_criterion_golden.py), the kernel's closed form (grad_cases'
+numpy mirror of csrc/criterion.hip) against float64 autograd within the gate the GPU tests use, argument errors, and
+the C ABI's symbol list."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import grad_cases as gc
+from conftest import GOLDEN, REPO
+
+CASES = ("n3", "n257", "n4096", "n4101", "sil", "one")
+
+
+@pytest.fixture(scope="module")
+def g():
+    return np.load(os.path.join(GOLDEN, "golden_train_criterion.npz"))
+
+
+def signals(g, tag):
+    if tag == "n4096":
+        return g["n4101_est"][:, :, :4096], g["n4101_tgt"][:, :, :4096]
+    return g[f"{tag}_est"], g[f"{tag}_tgt"]
+
+
+def rel_rowmax(got, ref):
+    ref = torch.as_tensor(ref)
+    d = (torch.as_tensor(got) - ref).abs().amax(-1)
+    return float((d / ref.abs().amax(-1).clamp(min=1e-300)).max())
+
+
+@pytest.mark.parametrize("tag", CASES)
+def test_restatement_reproduces_the_reference_autograd(g, tag):
+    est, tgt = (torch.from_numpy(np.ascontiguousarray(a)) for a in signals(g, tag))
+    vad, lab = torch.from_numpy(g[f"{tag}_vad"]), torch.from_numpy(g[f"{tag}_labels"])
+    r, ge, gv = gc.autograd_truth(est, tgt, vad, lab)
+    assert torch.equal(r["perm"], torch.from_numpy(g[f"{tag}_idx"]))
+    assert abs(r["sep"].item() - float(g[f"{tag}_sep_f64"])) <= 1e-9 * abs(float(g[f"{tag}_sep_f64"]))
+    assert abs(r["vad"].item() - float(g[f"{tag}_vadloss_f64"])) <= 1e-9 * abs(float(g[f"{tag}_vadloss_f64"]))
+    assert rel_rowmax(ge, g[f"{tag}_grad_est_f64"]) <= 1e-9
+    assert rel_rowmax(gv, g[f"{tag}_grad_vad_f64"]) <= 1e-9
+    if tag in ("sil", "one"):
+        zero = ge[:2] if tag == "sil" else ge
+        assert bool(torch.isfinite(ge).all()) and not bool(zero.any())
+
+
+@pytest.mark.parametrize("case", gc.PW_CASES, ids=lambda c: gc.pw_key(*c))
+def test_restatement_reproduces_every_pairwise_loss(g, case):
+    key = gc.pw_key(*case)
+    est, tgt = torch.from_numpy(g["n257_est"]), torch.from_numpy(g["n257_tgt"])
+    r, ge, _ = gc.autograd_truth(est, tgt, sdr_type=case[0], zero_mean=case[1], take_log=case[2])
+    assert torch.equal(r["perm"], torch.from_numpy(g[f"n257_{key}_idx"]))
+    assert rel_rowmax(ge, g[f"n257_{key}_grad_est_f64"]) <= 1e-9
+
+
+@pytest.mark.parametrize("tag", CASES)
+def test_mirror_meets_the_gate_on_the_fixture(g, tag):
+    est, tgt = signals(g, tag)
+    r, _, _ = gc.autograd_truth(torch.from_numpy(np.ascontiguousarray(est)), torch.from_numpy(np.ascontiguousarray(tgt)))
+    g64, idx = torch.from_numpy(g[f"{tag}_grad_est_f64"]), g[f"{tag}_idx"]
+    worst, _ = gc.est_error_in_gates(gc.mirror_grad_est(est, tgt, idx), g64, r["sdr_db"])
+    print(tag, "mirror error / gate:", worst)
+    assert worst <= 1.0
+    ok, rel = gc.vad_within_gate(gc.mirror_grad_vad(g[f"{tag}_vad"], g[f"{tag}_labels"], idx), torch.from_numpy(g[f"{tag}_grad_vad_f64"]))
+    print(tag, "mirror VAD worst relative error:", rel)
+    assert ok
+
+
+@pytest.mark.parametrize("case", gc.PW_CASES, ids=lambda c: gc.pw_key(*c))
+def test_mirror_meets_the_gate_for_every_pairwise_loss(g, case):
+    key = gc.pw_key(*case)
+    kw = dict(sdr_type=case[0], zero_mean=case[1], take_log=case[2])
+    r, _, _ = gc.autograd_truth(torch.from_numpy(g["n257_est"]), torch.from_numpy(g["n257_tgt"]), **kw)
+    got = gc.mirror_grad_est(g["n257_est"], g["n257_tgt"], g[f"n257_{key}_idx"], **kw)
+    worst, _ = gc.est_error_in_gates(got, torch.from_numpy(g[f"n257_{key}_grad_est_f64"]), r["sdr_db"])
+    print(key, "mirror error / gate:", worst)
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("sdr_db,dc", gc.regime_grid())
+def test_mirror_reaches_the_gate(sdr_db, dc):
+    """The gate is reachable by the kernel's arithmetic in every regime, before any GPU run; prints the table's row."""
+    est, tgt = gc.regime_case(sdr_db, dc)
+    r, g64, _ = gc.autograd_truth(est, tgt)
+    assert r["perm"].tolist() == [[0, 1], [1, 0]] and float((r["sdr_db"] - sdr_db).abs().max()) < 1.0
+    worst, ulps = gc.est_error_in_gates(gc.mirror_grad_est(est.numpy(), tgt.numpy(), r["perm"].numpy()), g64, r["sdr_db"])
+    gate_ulps = (gc.EST_GATE_ROUND + gc.EST_GATE_CANCEL * 10.0 ** (sdr_db / 10.0)) * 2.0 ** 24
+    print(f"SDR {sdr_db} dB, DC {dc} sigma: mirror worst {float(ulps.max()):.2f} x 2^-24 rowmax, gate {gate_ulps:.1f}")
+    assert worst <= 1.0
+    # what the gate replaces: float32 autograd of the same formulation
+    e32 = est.clone().requires_grad_(True)
+    gc.restated_criterion(e32, tgt)["sep"].backward()
+    _, ulps32 = gc.est_error_in_gates(e32.grad, g64, r["sdr_db"])
+    print(f"    float32 autograd: worst {float(ulps32.max()) * 2.0 ** -24:.1e} of rowmax")
+
+
+def criteria():
+    from sep_tfanet_vad_amd import combined_loss, pit, sdr
+    return (pit.PITLossWrapper(sdr.pairwise_neg_sisdr, pit_from="pw_mtx", perm_reduce=None),
+            pit.PITLossWrapper(combined_loss.BinaryCrossEntropyLoss_Mean(), pit_from="pw_pt"))
+
+
+WEIGHTS = dict(weight_separation_loss=0.99, weight_vad_loss=0.01, learn_weight_bool=False)
+
+
+def test_constructor_reads_settings_and_refuses_other_criteria():
+    from sep_tfanet_vad_amd import metrics, pit, sdr, train_criterion as tc
+    sep, vad = criteria()
+    crit = tc.CombinedLoss(sep, vad, dict(WEIGHTS))
+    assert crit._settings == ("sisdr", True, True, 1e-8) and not list(crit.parameters())
+    other = tc.CombinedLoss(pit.PITLossWrapper(sdr.PairwiseNegSDR("snr", zero_mean=False, take_log=False, EPS=1e-6), "pw_mtx"),
+                            vad, dict(WEIGHTS, learn_weight_bool=True))
+    assert other._settings == ("snr", False, False, 1e-6)
+    assert sorted(n for n, _ in other.named_parameters()) == ["learn_weight_separationLoss", "learn_weight_vadLoss"]
+    for bad in (pit.PITLossWrapper(torch.nn.L1Loss(), pit_from="pw_pt"),
+                pit.PITLossWrapper(metrics.calc_sisdr_loss, pit_from="pw_pt"),
+                pit.PITLossWrapper(sdr.pairwise_neg_sisdr, pit_from="pw_pt"),
+                pit.PITLossWrapper(sdr.pairwise_neg_sisdr, pit_from="pw_mtx", perm_reduce=torch.mean), sdr.pairwise_neg_sisdr):
+        with pytest.raises(NotImplementedError):
+            tc.CombinedLoss(bad, vad, dict(WEIGHTS))
+    with pytest.raises(NotImplementedError):
+        tc.CombinedLoss(sep, sep, dict(WEIGHTS))
+    for name in ("CombinedLoss", "BinaryCrossEntropyLoss_Mean", "reorder_source_mse", "calc_sisdr", "calc_sisdr_loss"):
+        assert hasattr(tc, name), name  # what train.py and the trainer take from model.combined_loss
+
+
+def test_argument_errors_raise_without_a_device():
+    from sep_tfanet_vad_amd import train_criterion as tc
+    crit = tc.CombinedLoss(*criteria(), dict(WEIGHTS))
+    x, v = torch.randn(2, 2, 100), torch.rand(2, 2, 5)
+    with pytest.raises(TypeError):
+        crit(x, x[:, :, :99], v, v)
+    with pytest.raises(TypeError):
+        crit(x[0], x[0], v, v)
+    with pytest.raises(NotImplementedError):
+        crit(torch.randn(2, 3, 100), torch.randn(2, 3, 100), v, v)
+    with pytest.raises(ValueError):
+        crit(x, x, v, v[:, :, :4])
+    with pytest.raises(ValueError):
+        crit(x, x, v[:1], v[:1])
+    with pytest.raises(RuntimeError, match="target requires grad"):
+        crit(x, x.clone().requires_grad_(True), v, v)
+    with pytest.raises(RuntimeError, match="target requires grad"):
+        crit(x, x, v, v.clone().requires_grad_(True))
+    with pytest.raises(RuntimeError, match="ROCm"):
+        crit(x.clone().requires_grad_(True), x, v, v)
+
+
+def test_exported_symbols_match_the_header():
+    from sep_tfanet_vad_amd import native, train_criterion
+    src = open(os.path.join(REPO, "include", "sepvad.h")).read()
+    syms = set(re.findall(r"\b(sepvad_[a-z0-9_]+)\s*\(", src))
+    assert {"sepvad_criterion_coef", "sepvad_criterion_backward"} <= syms
+    assert syms == set(native.EXPORTED_SYMBOLS)
+    assert int(re.search(r"SEPVAD_CRIT_COEF\s*=\s*(\d+)", src).group(1)) == train_criterion.CRIT_COEF
