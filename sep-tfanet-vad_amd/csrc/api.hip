@@ -33,6 +33,44 @@ SiSdrArgs sisdr_args(const float* P, int64_t p_ld, const float* Tg, int64_t t_ld
   a.zero_mean = zero_mean; a.out = out;
   return a;
 }
+// sepvad_si_sdr and sepvad_snr: one argument list and one check, `launch` the entry's kernel launcher
+int32_t pair_metric(const char* entry, hipError_t (*launch)(const SiSdrArgs&, hipStream_t), const float* P, int64_t p_ld,
+                    const float* Tg, int64_t t_ld, int64_t N, int32_t R, const int32_t* pidx, const int32_t* tidx,
+                    int32_t zero_mean, float* out, void* stream) {
+  if (!P || !Tg || !out || N < 1 || R < 1 || p_ld < N || t_ld < N)
+    return fail(SEPVAD_E_ARG, std::string(entry) + ": bad arguments");
+  HIPRET(launch(sisdr_args(P, p_ld, Tg, t_ld, N, R, pidx, tidx, zero_mean, out), (hipStream_t)stream));
+}
+
+// The eval family: sepvad_eval_separation, sepvad_criterion_coef and, for what it shares, sepvad_stream_eval.
+int64_t eval_chunks(int64_t N) { return (N + EV_CHUNK - 1) / EV_CHUNK; }
+int64_t eval_scratch(int32_t B, int64_t N) {
+  return (int64_t)B * (eval_chunks(N) * EV_MOM + EV_ROWVALS) * (int64_t)sizeof(double);
+}
+// Its argument checks, in the order the entries always made them; the message starts with `entry`. B utterances of N
+// samples in rows whose smallest stride is min_ld; se_need > 0: sepvad_stream_eval, whose shapes se_layout has
+// checked and whose scratch holds se_need bytes.
+int32_t eval_check(const char* entry, int32_t B, int64_t N, int64_t min_ld, int32_t sdr_type, const void* scratch,
+                   int64_t scratch_bytes, int64_t se_need = 0) {
+  const std::string e = std::string(entry) + ": ";
+  if (!se_need) {
+    if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40)) return fail(SEPVAD_E_ARG, e + "need 1 <= B <= 65535, 1 <= N <= 2^40");
+    if (min_ld < N) return fail(SEPVAD_E_ARG, e + "row strides must be >= N");
+  }
+  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, e + "unknown sdr_type");
+  if (scratch_bytes < (se_need ? se_need : eval_scratch(B, N)))
+    return fail(SEPVAD_E_ARG, e + "scratch too small (sepvad_" + (se_need ? "stream_eval" : "eval") + "_scratch_bytes)");
+  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(SEPVAD_E_ARG, e + "scratch must be 8-byte aligned");
+  return SEPVAD_OK;
+}
+// The criterion fields of EvalSepArgs / CritCoefArgs; partial: the moments' partials [B][nchunk][EV_MOM]
+template <typename Args, typename Partial>
+void set_criterion(Args& a, int32_t B, int64_t N, int32_t sdr_type, int32_t zero_mean, int32_t take_log, double eps,
+                   Partial* partial) {
+  a.B = B; a.N = N; a.nchunk = (int)eval_chunks(N);
+  a.sdr_type = sdr_type; a.zero_mean = zero_mean != 0; a.take_log = take_log != 0; a.eps = eps;
+  a.partial = partial;
+}
 }  // namespace
 
 void sepvad::set_error(const std::string& msg) { g_err = msg; }
@@ -409,14 +447,12 @@ int32_t sepvad_resample(const float* x, int64_t n, const float* taps, const int3
 
 int32_t sepvad_si_sdr(const float* P, int64_t p_ld, const float* Tg, int64_t t_ld, int64_t N, int32_t R,
                       const int32_t* pidx, const int32_t* tidx, int32_t zero_mean, float* out, void* stream) {
-  if (!P || !Tg || !out || N < 1 || R < 1 || p_ld < N || t_ld < N) return fail(SEPVAD_E_ARG, "sepvad_si_sdr: bad arguments");
-  HIPRET(launch_si_sdr(sisdr_args(P, p_ld, Tg, t_ld, N, R, pidx, tidx, zero_mean, out), (hipStream_t)stream));
+  return pair_metric("sepvad_si_sdr", launch_si_sdr, P, p_ld, Tg, t_ld, N, R, pidx, tidx, zero_mean, out, stream);
 }
 
 int32_t sepvad_snr(const float* P, int64_t p_ld, const float* Tg, int64_t t_ld, int64_t N, int32_t R,
                    const int32_t* pidx, const int32_t* tidx, int32_t zero_mean, float* out, void* stream) {
-  if (!P || !Tg || !out || N < 1 || R < 1 || p_ld < N || t_ld < N) return fail(SEPVAD_E_ARG, "sepvad_snr: bad arguments");
-  HIPRET(launch_snr(sisdr_args(P, p_ld, Tg, t_ld, N, R, pidx, tidx, zero_mean, out), (hipStream_t)stream));
+  return pair_metric("sepvad_snr", launch_snr, P, p_ld, Tg, t_ld, N, R, pidx, tidx, zero_mean, out, stream);
 }
 
 int32_t sepvad_stoi_filter(int32_t fs_sig, float* taps, int32_t cap, int32_t* info) {
@@ -475,11 +511,6 @@ int32_t sepvad_vad_accuracy(float* preds, const float* targets, int32_t B, int32
   HIPRET(launch_vad_acc(a, (hipStream_t)stream));
 }
 
-static int64_t eval_chunks(int64_t N) { return (N + EV_CHUNK - 1) / EV_CHUNK; }
-static int64_t eval_scratch(int32_t B, int64_t N) {
-  return (int64_t)B * (eval_chunks(N) * EV_MOM + EV_ROWVALS) * (int64_t)sizeof(double);
-}
-
 int64_t sepvad_eval_scratch_bytes(int32_t B, int64_t N) {
   if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40))
     return fail(SEPVAD_E_ARG, "sepvad_eval_scratch_bytes: need 1 <= B <= 65535, 1 <= N <= 2^40");
@@ -494,16 +525,12 @@ int32_t sepvad_eval_separation(const float* est, int64_t est_ld, const float* tg
                                float* min_loss, int64_t* perm, float* sheet, float* means, void* stream) {
   if (!est || !tgt || !scratch || !pw || !min_loss || !perm || !means)
     return fail(SEPVAD_E_ARG, "sepvad_eval_separation: null pointer");
-  if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40)) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: need 1 <= B <= 65535, 1 <= N <= 2^40");
-  if (est_ld < N || tgt_ld < N || (mix && mix_ld < N)) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: row strides must be >= N");
-  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: unknown sdr_type");
-  if (scratch_bytes < eval_scratch(B, N)) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: scratch too small (sepvad_eval_scratch_bytes)");
-  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(SEPVAD_E_ARG, "sepvad_eval_separation: scratch must be 8-byte aligned");
+  if (const int32_t rc = eval_check("sepvad_eval_separation", B, N, std::min({est_ld, tgt_ld, mix ? mix_ld : N}), sdr_type,
+                                    scratch, scratch_bytes))
+    return rc;
   EvalSepArgs a{};
   a.est = est; a.est_ld = est_ld; a.tgt = tgt; a.tgt_ld = tgt_ld; a.mix = mix; a.mix_ld = mix_ld;
-  a.B = B; a.N = N; a.nchunk = (int)eval_chunks(N);
-  a.sdr_type = sdr_type; a.zero_mean = zero_mean != 0; a.take_log = take_log != 0; a.eps = eps;
-  a.partial = (double*)scratch;
+  set_criterion(a, B, N, sdr_type, zero_mean, take_log, eps, (double*)scratch);
   a.rowvals = a.partial + (int64_t)B * a.nchunk * EV_MOM;
   a.pw = pw; a.min_loss = min_loss; a.perm = (long long*)perm; a.sheet = sheet; a.means = means;
   HIPRET(launch_eval_separation(a, (hipStream_t)stream));
@@ -554,9 +581,7 @@ int32_t sepvad_stream_eval(const float* sep, int64_t sep_ld, int32_t n, int32_t 
   if (k0 < 0 || K < 1 || (int64_t)k0 + n > K) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: need 0 <= k0 and k0 + n <= K");
   if (sep_ld < W || tgt_ld < (int64_t)(K - 1) * H + W || raw_ld < (int64_t)K * H || online_ld < (int64_t)K * H)
     return fail(SEPVAD_E_ARG, "sepvad_stream_eval: row strides must cover W (sep), (K - 1) H + W (tgt) and K H (raw, online)");
-  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: unknown sdr_type");
-  if (scratch_bytes < L.total) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: scratch too small (sepvad_stream_eval_scratch_bytes)");
-  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: scratch must be 8-byte aligned");
+  if (const int32_t rc = eval_check("sepvad_stream_eval", n * B, W, W, sdr_type, scratch, scratch_bytes, L.total)) return rc;
   StreamEvalArgs a{};
   a.B = B; a.n = n; a.k0 = k0; a.K = K; a.mode = mode; a.W = W; a.H = H; a.S = L.S;
   a.sep = sep; a.sep_ld = sep_ld; a.raw = raw; a.raw_ld = raw_ld; a.online = online; a.on_ld = online_ld;
@@ -568,9 +593,8 @@ int32_t sepvad_stream_eval(const float* sep, int64_t sep_ld, int32_t n, int32_t 
   const int64_t w0 = (int64_t)k0 * B;  // the per-window outputs of this chunk start at window k0
   EvalSepArgs& e = a.ev;
   e.est = sep; e.est_ld = sep_ld; e.tgt = tgt + (int64_t)k0 * H; e.tgt_ld = tgt_ld;
-  e.B = n * B; e.N = W; e.nchunk = L.nchunk;
-  e.sdr_type = sdr_type; e.zero_mean = zero_mean != 0; e.take_log = take_log != 0; e.eps = eps;
-  e.partial = sc + L.partial; e.rowvals = sc + L.rowvals;
+  set_criterion(e, n * B, W, sdr_type, zero_mean, take_log, eps, sc + L.partial);  // nchunk == L.nchunk
+  e.rowvals = sc + L.rowvals;
   e.pw = pw_tgt + w0 * 4; e.min_loss = loss_tgt + w0;
   e.perm = (long long*)(mode == SEPVAD_SE_NONE ? perm : perm_tgt) + w0 * 2;
   HIPRET(launch_stream_eval(a, (hipStream_t)stream));
@@ -600,16 +624,12 @@ int32_t sepvad_criterion_coef(const float* est, int64_t est_ld, const float* tgt
                               int32_t sdr_type, int32_t zero_mean, int32_t take_log, double eps, const void* scratch,
                               int64_t scratch_bytes, const int64_t* perm, double* coef, void* stream) {
   if (!est || !tgt || !scratch || !perm || !coef) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: null pointer");
-  if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40)) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: need 1 <= B <= 65535, 1 <= N <= 2^40");
-  if (est_ld < N || tgt_ld < N) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: row strides must be >= N");
-  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: unknown sdr_type");
-  if (scratch_bytes < eval_scratch(B, N)) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: scratch too small (sepvad_eval_scratch_bytes)");
-  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(SEPVAD_E_ARG, "sepvad_criterion_coef: scratch must be 8-byte aligned");
+  if (const int32_t rc = eval_check("sepvad_criterion_coef", B, N, std::min(est_ld, tgt_ld), sdr_type, scratch, scratch_bytes))
+    return rc;
   CritCoefArgs a{};
   a.est = est; a.est_ld = est_ld; a.tgt = tgt; a.tgt_ld = tgt_ld;
-  a.B = B; a.N = N; a.nchunk = (int)eval_chunks(N);
-  a.sdr_type = sdr_type; a.zero_mean = zero_mean != 0; a.take_log = take_log != 0; a.eps = eps;
-  a.partial = (const double*)scratch; a.perm = (const long long*)perm; a.coef = coef;
+  set_criterion(a, B, N, sdr_type, zero_mean, take_log, eps, (const double*)scratch);
+  a.perm = (const long long*)perm; a.coef = coef;
   HIPRET(launch_crit_coef(a, (hipStream_t)stream));
 }
 

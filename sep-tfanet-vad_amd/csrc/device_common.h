@@ -112,6 +112,38 @@ __device__ __forceinline__ void block_reduce_store(float (&v)[NV], float* lds, d
   }
 }
 
+// The double-precision sibling for the scoring kernels (blockDim == 64 NW): wave w's sum of value k goes to
+// red[k * NW + w], one barrier, then thread k < NV adds its NW wave totals in wave order and stores out[at + k].
+// `red` holds NV * NW doubles.
+template <int NV, int NW>
+__device__ __forceinline__ void block_sums_store(const double (&s)[NV], double* red, double* out, long long at = 0) {
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const double v = wave_sum(s[k]);
+    if (l == 0) red[k * NW + w] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    double v = 0.0;
+    for (int i = 0; i < NW; ++i) v += red[threadIdx.x * NW + i];
+    out[at + threadIdx.x] = v;
+  }
+}
+
+// Four consecutive samples 4 q .. 4 q + 3 of row p: one float4 load (VEC: p is 16-byte aligned) or four scalar ones.
+// q keeps the caller's index type, so a 32-bit caller gets no 64-bit address arithmetic.
+template <bool VEC, typename Ti>
+__device__ __forceinline__ void load4(const float* p, Ti q, float (&v)[4]) {
+  if (VEC) {
+    const float4 f = reinterpret_cast<const float4*>(p)[q];
+    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = p[4 * q + k];
+  }
+}
+
 // dst[0, n) = src[0, n) by threads tid, tid + nth, ...: float4 where both pointers are 16-byte aligned (the last
 // n % 4 scalar), scalar otherwise (stream.hip, stream_eval.hip)
 __device__ __forceinline__ void copy_run(float* dst, const float* src, long long n, long long tid, long long nth) {

@@ -12,18 +12,11 @@ constexpr int EV_THREADS = 256;
 constexpr int EVM_S = 0, EVM_Q = 5, EVM_ET = 10, EVM_MT = 14;
 static_assert(EV_CHUNK % 4 == 0, "chunk bases must keep a row's 16-byte alignment");
 
-// four consecutive samples 4 q .. 4 q + 3 of row p (null: zeros)
+// load4 of a nullable row (null: zeros)
 template <bool VEC>
 __device__ __forceinline__ void ev_load4(const float* p, int q, float (&v)[4]) {
-  if (!p) {
-    v[0] = v[1] = v[2] = v[3] = 0.f;
-  } else if (VEC) {
-    const float4 f = reinterpret_cast<const float4*>(p)[q];
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = p[4 * q + k];
-  }
+  if (!p) v[0] = v[1] = v[2] = v[3] = 0.f;
+  else load4<VEC>(p, q, v);
 }
 
 // explicit fma: the same rounding in both paths whatever the compiler contracts; c: the five rows' first samples
@@ -76,18 +69,7 @@ __device__ __forceinline__ void ev_block_moments(const float* e0, const float* e
                          reinterpret_cast<uintptr_t>(m);
   if ((bits & 15) == 0) ev_chunk<true>(e0, e1, t0, t1, m, len, piv, s);
   else ev_chunk<false>(e0, e1, t0, t1, m, len, piv, s);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < EV_MOM; ++k) {
-    const double v = wave_sum(s[k]);
-    if (l == 0) red[k * (EV_THREADS / 64) + w] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < EV_MOM) {
-    double v = 0.0;
-    for (int i = 0; i < EV_THREADS / 64; ++i) v += red[threadIdx.x * (EV_THREADS / 64) + i];
-    out[threadIdx.x] = v;
-  }
+  block_sums_store<EV_MOM, EV_THREADS / 64>(s, red, out);
 }
 
 // <x, y> of the rows themselves from the moments of x - cx and y - cy. One expression for <p,p>, <t,t> and <p,t>:

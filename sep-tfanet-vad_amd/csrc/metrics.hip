@@ -26,18 +26,6 @@ namespace sepvad {
 
 constexpr int SD_THREADS = 256;
 
-// four consecutive samples 4 q .. 4 q + 3 of a row
-template <bool VEC>
-__device__ __forceinline__ void sd_load4(const float* p, long long q, float (&v)[4]) {
-  if (VEC) {
-    const float4 f = reinterpret_cast<const float4*>(p)[q];
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = p[4 * q + k];
-  }
-}
-
 // explicit fma: the same rounding in both paths whatever the compiler contracts
 __device__ __forceinline__ void sd_acc(double (&s)[5], float pf, float tf, double cp, double ct) {
   const double x = (double)pf - cp, y = (double)tf - ct;
@@ -55,7 +43,7 @@ __device__ __forceinline__ void sd_row(const float* p, const float* t, long long
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long long q = q0 + u * SD_THREADS;
-      if (q < n4) { sd_load4<VEC>(p, q, pa[u]); sd_load4<VEC>(t, q, ta[u]); }
+      if (q < n4) { load4<VEC>(p, q, pa[u]); load4<VEC>(t, q, ta[u]); }
     }
     double c[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll

@@ -107,18 +107,7 @@ __device__ __forceinline__ void se_segment(const StreamEvalArgs& a, int kl, int 
     if ((bits & 15) == 0) se_span<MODE, true>(e0, e1, r0, r1, cnt, s);
     else se_span<MODE, false>(e0, e1, r0, r1, cnt, s);
   }
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-#pragma unroll
-  for (int v = 0; v < SE_NV; ++v) {
-    const double x = wave_sum(s[v]);
-    if (l == 0) red[v * (SE_THREADS / 64) + w] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < SE_NV) {
-    double x = 0.0;
-    for (int i = 0; i < SE_THREADS / 64; ++i) x += red[threadIdx.x * (SE_THREADS / 64) + i];
-    a.seg[(((long long)kl * a.S + j) * a.B + b) * SE_NV + threadIdx.x] = x;
-  }
+  block_sums_store<SE_NV, SE_THREADS / 64>(s, red, a.seg, (((long long)kl * a.S + j) * a.B + b) * SE_NV);
 }
 
 // window-utterance u = kl B + b of the chunk: its estimate rows and its target window

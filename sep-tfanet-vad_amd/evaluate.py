@@ -14,8 +14,6 @@ Forward-only: an input that requires grad under grad mode is refused. Inputs are
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import native as _native
@@ -27,19 +25,6 @@ SHEET_COLUMNS = ("si_sdr_speaker0", "si_sdr_speaker1", "si_sdr_start_speaker0", 
 MEANS = ("loss", "pit_si_sdr", "pit_snr", "si_sdri")  # SEPVAD_EV_MEAN_*
 MASK_BINS = 257
 
-_scratch = {}  # (device, stream) -> float64 scratch, most recently used last (as pit._scratch_for)
-
-
-def _scratch_for(device, nbytes):
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    buf = _scratch.pop(key, None)
-    if buf is None or buf.numel() * 8 < nbytes:
-        buf = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-        while len(_scratch) >= 32:
-            _scratch.pop(next(iter(_scratch)))
-    _scratch[key] = buf
-    return buf
-
 
 def refuse_grad(what, *tensors):
     """The native criterion has no backward: refuse inputs that would expect one."""
@@ -48,41 +33,12 @@ def refuse_grad(what, *tensors):
                            "torch.no_grad() or detach the inputs")
 
 
-def _device_of(what, first, *rest):
-    if first.device.type != "cuda":
-        raise RuntimeError(f"{what}: inputs must be ROCm device tensors")
-    for t in rest:
-        if t is not None and t.device != first.device:
-            raise RuntimeError(f"{what}: inputs must be on one ROCm device")
-    return first.device
-
-
-def _rows3(t):
-    """[B, 2, N] float32 with unit sample stride, speaker stride ld >= N and batch stride 2 ld -> (tensor, ld)."""
-    t = t.to(torch.float32)
-    B, _, N = t.shape
-    if t.stride(2) != 1 or t.stride(1) < N or (B > 1 and t.stride(0) != 2 * t.stride(1)):
-        t = t.contiguous()
-    return t, t.stride(1)
-
-
-def _rows2(t):
-    """[B, N] float32 with unit sample stride and row stride ld >= N -> (tensor, ld)."""
-    t = t.to(torch.float32)
-    B, N = t.shape
-    if t.stride(1) != 1 or (B > 1 and t.stride(0) < N):
-        t = t.contiguous()
-    return t, (t.stride(0) if B > 1 else N)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def eval_separation(est, tgt, mix=None, sdr_type="sisdr", zero_mean=True, take_log=True, eps=1e-8, sheet=True):
+def eval_separation(est, tgt, mix=None, sdr_type="sisdr", zero_mean=True, take_log=True, eps=1e-8, sheet=True,
+                    scratch=None):
     """sepvad_eval_separation: est, tgt [B, 2, N], mix [B, N] or None -> dict of device tensors
     pw [B, 2, 2] (estimate i against target j), min_loss [B], perm [B, 2] int64 (perm[b, j] = the estimate assigned
-    to target j), sheet [B, 8] (SHEET_COLUMNS; None when sheet=False), means [4] (MEANS)."""
+    to target j), sheet [B, 8] (SHEET_COLUMNS; None when sheet=False), means [4] (MEANS), and scratch: the uint8 buffer
+    the call used (the argument, or the stream's shared one), whose moment partials sepvad_criterion_coef reads."""
     what = "eval_separation"
     if sdr_type not in SDR_TYPES:
         raise ValueError(f"{what}: sdr_type must be one of {sorted(SDR_TYPES)}, got {sdr_type!r}")
@@ -91,31 +47,30 @@ def eval_separation(est, tgt, mix=None, sdr_type="sisdr", zero_mean=True, take_l
                          f"{tuple(tgt.shape)}")
     if mix is not None and tuple(mix.shape) != (est.shape[0], est.shape[2]):
         raise ValueError(f"{what}: expected mix [B, N], got {tuple(mix.shape)}")
-    dev = _device_of(what, est, tgt, mix)
+    dev = _native.require_device(what, est, tgt, mix)
     refuse_grad(what, est, tgt, mix)
     lib = _native.load_library()
-    est, eld = _rows3(est)
-    tgt, tld = _rows3(tgt)
+    est, eld = _native.rows3(est)
+    tgt, tld = _native.rows3(tgt)
     mld = 0
     if mix is not None:
-        mix, mld = _rows2(mix)
+        mix, mld = _native.rows2(mix)
     B, _, N = est.shape
-    nbytes = int(lib.sepvad_eval_scratch_bytes(B, N))
-    if nbytes < 0:
-        _native._check(nbytes, "sepvad_eval_scratch_bytes")
-    scratch = _scratch_for(dev, nbytes)
+    if scratch is None:
+        scratch = _native.scratch(dev, _native.query_bytes(lib.sepvad_eval_scratch_bytes, "sepvad_eval_scratch_bytes",
+                                                           B, N))
     pw = torch.empty(B, 2, 2, dtype=torch.float32, device=dev)
     min_loss = torch.empty(B, dtype=torch.float32, device=dev)
     perm = torch.empty(B, 2, dtype=torch.int64, device=dev)
     sh = torch.empty(B, len(SHEET_COLUMNS), dtype=torch.float32, device=dev) if sheet else None
     means = torch.empty(len(MEANS), dtype=torch.float32, device=dev)
-    rc = lib.sepvad_eval_separation(_native._ptr(est), eld, _native._ptr(tgt), tld, _native._ptr(mix), mld, B, N,
+    rc = lib.sepvad_eval_separation(_native.ptr(est), eld, _native.ptr(tgt), tld, _native.ptr(mix), mld, B, N,
                                     SDR_TYPES[sdr_type], int(bool(zero_mean)), int(bool(take_log)), float(eps),
-                                    _native._ptr(scratch), scratch.numel() * 8, _native._ptr(pw),
-                                    _native._ptr(min_loss), _native._ptr(perm), _native._ptr(sh), _native._ptr(means),
-                                    _stream(dev))
-    _native._check(rc, "sepvad_eval_separation")
-    return dict(pw=pw, min_loss=min_loss, perm=perm, sheet=sh, means=means)
+                                    _native.ptr(scratch), scratch.numel(), _native.ptr(pw),
+                                    _native.ptr(min_loss), _native.ptr(perm), _native.ptr(sh), _native.ptr(means),
+                                    _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_eval_separation")
+    return dict(pw=pw, min_loss=min_loss, perm=perm, sheet=sh, means=means, scratch=scratch)
 
 
 def _perm_arg(what, perm, B, dev):
@@ -136,7 +91,7 @@ def eval_vad(vad, labels, perm=None, masks=None, fix_labels=True):
     if vad.dim() != 3 or vad.shape[1] != 2 or vad.shape != labels.shape:
         raise ValueError(f"{what}: expected vad and labels of one shape [B, 2, T], got {tuple(vad.shape)} and "
                          f"{tuple(labels.shape)}")
-    dev = _device_of(what, vad, labels, masks)
+    dev = _native.require_device(what, vad, labels, masks)
     refuse_grad(what, vad, labels, masks)
     B, _, T = vad.shape
     if masks is not None and tuple(masks.shape) != (B, 2, MASK_BINS, T):
@@ -156,11 +111,11 @@ def eval_vad(vad, labels, perm=None, masks=None, fix_labels=True):
         masks = masks.to(torch.float32).contiguous()
         simple = torch.empty(B, 2, T, dtype=torch.int64, device=dev)
         conf_simple = torch.empty(B, 2, 4, dtype=torch.int32, device=dev)
-    rc = lib.sepvad_eval_vad(_native._ptr(vad), _native._ptr(lab), int(bool(fix_labels)), _native._ptr(perm),
-                             _native._ptr(masks), B, T, _native._ptr(bce_rows), _native._ptr(bce_mean),
-                             _native._ptr(pw_ce), _native._ptr(conf), _native._ptr(simple), _native._ptr(conf_simple),
-                             _stream(dev))
-    _native._check(rc, "sepvad_eval_vad")
+    rc = lib.sepvad_eval_vad(_native.ptr(vad), _native.ptr(lab), int(bool(fix_labels)), _native.ptr(perm),
+                             _native.ptr(masks), B, T, _native.ptr(bce_rows), _native.ptr(bce_mean),
+                             _native.ptr(pw_ce), _native.ptr(conf), _native.ptr(simple), _native.ptr(conf_simple),
+                             _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_eval_vad")
     out = dict(bce_rows=bce_rows, bce_mean=bce_mean, pw_ce=pw_ce, conf=conf, labels=lab)
     if masks is not None:
         out.update(simple_vad=simple, conf_simple=conf_simple)
@@ -186,16 +141,16 @@ def simple_vad(masks, perm=None):
     what = "calc_vad"
     if masks.dim() != 4 or masks.shape[1] != 2 or masks.shape[2] != MASK_BINS:
         raise NotImplementedError(f"{what}: built for masks [B, 2, {MASK_BINS}, T], got {tuple(masks.shape)}")
-    dev = _device_of(what, masks)
+    dev = _native.require_device(what, masks)
     refuse_grad(what, masks)
     B, _, _, T = masks.shape
     lib = _native.load_library()
     masks = masks.to(torch.float32).contiguous()
     perm = _perm_arg(what, perm, B, dev)
     simple = torch.empty(B, 2, T, dtype=torch.int64, device=dev)
-    rc = lib.sepvad_eval_vad(None, None, 0, _native._ptr(perm), _native._ptr(masks), B, T, None, None, None, None,
-                             _native._ptr(simple), None, _stream(dev))
-    _native._check(rc, "sepvad_eval_vad")
+    rc = lib.sepvad_eval_vad(None, None, 0, _native.ptr(perm), _native.ptr(masks), B, T, None, None, None, None,
+                             _native.ptr(simple), None, _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_eval_vad")
     return simple
 
 
@@ -215,6 +170,7 @@ def score_batch(sep, target, mix=None, vad=None, labels=None, masks=None, sdr_ty
     if (vad is None) != (labels is None):
         raise ValueError("score_batch: vad and labels go together")
     out = eval_separation(sep, target, mix, sdr_type=sdr_type)
+    del out["scratch"]
     for i, name in enumerate(MEANS):
         if name != "si_sdri" or mix is not None:
             out[name] = out["means"][i]

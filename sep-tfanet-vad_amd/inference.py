@@ -47,18 +47,14 @@ DEFAULT_INFERENCE_KW = {
 NORM_SCRATCH_BYTES = 8192  # SEPVAD_NORM_SCRATCH_BYTES (include/sepvad.h)
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def resample_filter(orig_freq: int, new_freq: int):
     """Host taps [phases, ntaps] and info (phases, ntaps, stride, width) of Resample(orig, new)."""
     lib = _native.load_library()
     info = (ctypes.c_int32 * 4)()
-    _native._check(lib.sepvad_resample_filter(int(orig_freq), int(new_freq), None, 0, info), "sepvad_resample_filter")
+    _native.check(lib.sepvad_resample_filter(int(orig_freq), int(new_freq), None, 0, info), "sepvad_resample_filter")
     phases, ntaps = info[0], info[1]
     taps = np.empty(phases * ntaps, dtype=np.float32)
-    _native._check(lib.sepvad_resample_filter(int(orig_freq), int(new_freq), taps.ctypes.data_as(ctypes.POINTER(
+    _native.check(lib.sepvad_resample_filter(int(orig_freq), int(new_freq), taps.ctypes.data_as(ctypes.POINTER(
         ctypes.c_float)), taps.size, info), "sepvad_resample_filter")
     return taps.reshape(phases, ntaps), tuple(info)
 
@@ -75,9 +71,9 @@ def resample(x: torch.Tensor, orig_freq: int, new_freq: int = 16000) -> torch.Te
     y = torch.empty(ylen, dtype=torch.float32, device=x.device)
     t = torch.from_numpy(taps).to(x.device)
     cinfo = (ctypes.c_int32 * 4)(*info)  # host array read by the C entry point
-    rc = lib.sepvad_resample(_native._ptr(x), x.numel(), _native._ptr(t), cinfo, _native._ptr(y), ylen,
-                             _stream(x.device))
-    _native._check(rc, "sepvad_resample")
+    rc = lib.sepvad_resample(_native.ptr(x), x.numel(), _native.ptr(t), cinfo, _native.ptr(y), ylen,
+                             _native.stream_ptr(x.device))
+    _native.check(rc, "sepvad_resample")
     return y
 
 
@@ -89,8 +85,8 @@ def normalize(x: torch.Tensor) -> torch.Tensor:
     x = x.float().contiguous()
     y = torch.empty_like(x)
     scratch = torch.empty(NORM_SCRATCH_BYTES // 4, dtype=torch.float32, device=x.device)
-    _native._check(lib.sepvad_normalize(_native._ptr(x), x.numel(), _native._ptr(y), _native._ptr(scratch),
-                                        _stream(x.device)), "sepvad_normalize")
+    _native.check(lib.sepvad_normalize(_native.ptr(x), x.numel(), _native.ptr(y), _native.ptr(scratch),
+                                        _native.stream_ptr(x.device)), "sepvad_normalize")
     return y
 
 

@@ -108,9 +108,8 @@ class LiveSeparator:
         self._tail = torch.empty(B, 2, 2 * self.Rt, dtype=torch.float32, device=self.device)
         nbytes = 0
         if self.per_stream:
-            nbytes = int(self._lib.sepvad_pit_l1_rows_scratch_bytes(B, self.win - self.hop))
-            if nbytes < 0:
-                _native._check(nbytes, "sepvad_pit_l1_rows_scratch_bytes")
+            nbytes = _native.query_bytes(self._lib.sepvad_pit_l1_rows_scratch_bytes, "sepvad_pit_l1_rows_scratch_bytes",
+                                         B, self.win - self.hop)
         self._scratch = torch.empty(max(nbytes, _pit.PIT_SCRATCH_BYTES) // 8, dtype=torch.float64, device=self.device)
         self._h.reserve(B * self.max_pending, self.win)
         self.reset()
@@ -124,7 +123,7 @@ class LiveSeparator:
     def _match_and_stitch(self, pred, vad, perm, loss, out, vad_out, j, stream):
         B, win, hop, Rt = self.n_streams, self.win, self.hop, self.Rt
         k = self.windows_done
-        P = _native._ptr
+        P = _native.ptr
         filled = k * hop
         n_on = hop if k == 0 else filled                      # calc_online: window 0 meets its own last hop
         pb, pe = _slice_bounds(win, -hop - n_on, -hop)        # reference :87
@@ -139,16 +138,16 @@ class LiveSeparator:
         if self.per_stream:
             rc = self._lib.sepvad_pit_l1_rows(est, win, ref, ref_ld, B, L, P(self._scratch),
                                               self._scratch.numel() * 8, P(perm), P(loss), None, stream)
-            _native._check(rc, "sepvad_pit_l1_rows")
+            _native.check(rc, "sepvad_pit_l1_rows")
         else:
             rc = self._lib.sepvad_pit_l1(est, win, ref, ref_ld, B, L, P(self._scratch), P(perm), P(loss), None, stream)
-            _native._check(rc, "sepvad_pit_l1")
+            _native.check(rc, "sepvad_pit_l1")
         nf = self.vad_frames
         rc = self._lib.sepvad_live_stitch(P(pred), win, win, B, hop, P(perm), P(out), out.stride(1), j * hop,
                                           P(self._tail), Rt, filled % Rt,
                                           P(vad) if nf else None, self.T, nf,
                                           P(vad_out) if nf else None, vad_out.stride(1) if nf else 0, j * nf, stream)
-        _native._check(rc, "sepvad_live_stitch")
+        _native.check(rc, "sepvad_live_stitch")
 
     def push(self, chunk: torch.Tensor):
         """chunk [n_streams, n] float32 on the device, any n >= 1 -> (sep [n_streams, 2, m * hop], vad
@@ -172,14 +171,14 @@ class LiveSeparator:
         vad_out = torch.empty(B, 2, m_total * nf, dtype=torch.float32, device=dev) if nf else None
         perm = torch.empty(m_total, B, 2, dtype=torch.int64, device=dev)
         loss = torch.empty(B, dtype=torch.float32, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _native.stream_ptr(dev)
         ld = chunk.stride(0) if B > 1 else n
         done = j = 0
         while done < n:
             take = min(n - done, push_room(self.samples_received, self.windows_done, hop, R))
             rc = self._lib.sepvad_ring_push(ctypes.c_void_p(chunk.data_ptr() + 4 * done), ld, B, take,
-                                            _native._ptr(self._ring), R, self.samples_received % R, stream)
-            _native._check(rc, "sepvad_ring_push")
+                                            _native.ptr(self._ring), R, self.samples_received % R, stream)
+            _native.check(rc, "sepvad_ring_push")
             self.samples_received += take
             done += take
             while True:

@@ -39,7 +39,7 @@ def _check_same_shape(preds, target):
                            f"{preds.shape} and target has shape of {target.shape}")
 
 
-def _rows(x: torch.Tensor) -> torch.Tensor:
+def _as_rows(x: torch.Tensor) -> torch.Tensor:
     if x.device.type != "cuda":
         raise RuntimeError("sepvad metrics: inputs must be ROCm device tensors")
     return x.to(torch.float32).reshape(-1, x.shape[-1]).contiguous()
@@ -53,10 +53,10 @@ def _si_sdr_pairs(P, Tg, pidx=None, tidx=None, zero_mean=True, entry="sepvad_si_
     out = torch.empty(R, device=P.device, dtype=torch.float32)
     pi = torch.as_tensor(pidx, dtype=torch.int32, device=P.device) if pidx is not None else None
     ti = torch.as_tensor(tidx, dtype=torch.int32, device=P.device) if tidx is not None else None
-    stream = torch.cuda.current_stream(P.device).cuda_stream
-    rc = getattr(lib, entry)(_native._ptr(P), P.shape[1], _native._ptr(Tg), Tg.shape[1], P.shape[1], R,
-                             _native._ptr(pi), _native._ptr(ti), int(bool(zero_mean)), _native._ptr(out), stream)
-    _native._check(rc, entry)
+    rc = getattr(lib, entry)(_native.ptr(P), P.shape[1], _native.ptr(Tg), Tg.shape[1], P.shape[1], R,
+                             _native.ptr(pi), _native.ptr(ti), int(bool(zero_mean)), _native.ptr(out),
+                             _native.stream_ptr(P.device))
+    _native.check(rc, entry)
     return out
 
 
@@ -67,7 +67,7 @@ def _snr_pairs(P, Tg, pidx=None, tidx=None, zero_mean=True):
 def scale_invariant_signal_distortion_ratio(preds: torch.Tensor, target: torch.Tensor, zero_mean: bool = True):
     """model/metric.py:61-101 (== model/combined_loss.py:16-56 calc_sisdr)."""
     _check_same_shape(preds, target)
-    P, Tg = _rows(preds), _rows(target)
+    P, Tg = _as_rows(preds), _as_rows(target)
     return _si_sdr_pairs(P, Tg, zero_mean=zero_mean).reshape(preds.shape[:-1])
 
 
@@ -82,7 +82,7 @@ def calc_sisdr_loss(preds, target, zero_mean: bool = True):
 def signal_noise_ratio(preds: torch.Tensor, target: torch.Tensor, zero_mean: bool = True):
     """model/metric.py:104-143 (note its default: zero_mean=True, unlike torchmetrics)."""
     _check_same_shape(preds, target)
-    P, Tg = _rows(preds), _rows(target)
+    P, Tg = _as_rows(preds), _as_rows(target)
     return _snr_pairs(P, Tg, zero_mean=zero_mean).reshape(preds.shape[:-1])
 
 
@@ -95,7 +95,7 @@ def permutation_invariant_si_sdr(preds: torch.Tensor, target: torch.Tensor, zero
     maximum over permutations in itertools order (torchmetrics' exhaustive search)."""
     _check_same_shape(preds, target)
     B, S, N = preds.shape
-    P, Tg = _rows(preds), _rows(target)
+    P, Tg = _as_rows(preds), _as_rows(target)
     pidx, tidx = [], []
     for b in range(B):
         for t in range(S):
@@ -132,20 +132,6 @@ pit_snr.to = lambda *args, **kwargs: pit_snr
 pit_si_sdr.to = lambda *args, **kwargs: pit_si_sdr
 
 
-_stoi_scratch = {}  # (device, stream) -> uint8 scratch, most recently used last (as pit._scratch_for)
-
-
-def _stoi_scratch_for(device, nbytes):
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    buf = _stoi_scratch.pop(key, None)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        while len(_stoi_scratch) >= 32:
-            _stoi_scratch.pop(next(iter(_stoi_scratch)))
-    _stoi_scratch[key] = buf
-    return buf
-
-
 def stoi_filter(fs_sig: int):
     """Host design of the STOI front end (sepvad_stoi_filter, no GPU): (taps float32 [ntaps] = h / sum(h) of
     stoi_metric.py:11-52, (up, down), bands int32 [15, 2] = first bin / one past the last bin of OBM, :201)."""
@@ -153,10 +139,10 @@ def stoi_filter(fs_sig: int):
     import numpy as np
     lib = _native.load_library()
     info = (ctypes.c_int32 * 34)()
-    _native._check(lib.sepvad_stoi_filter(int(fs_sig), None, 0, info), "sepvad_stoi_filter")
+    _native.check(lib.sepvad_stoi_filter(int(fs_sig), None, 0, info), "sepvad_stoi_filter")
     taps = np.zeros(info[2], np.float32)
-    _native._check(lib.sepvad_stoi_filter(int(fs_sig), taps.ctypes.data_as(ctypes.c_void_p), taps.size, info),
-                   "sepvad_stoi_filter")
+    _native.check(lib.sepvad_stoi_filter(int(fs_sig), taps.ctypes.data_as(ctypes.c_void_p), taps.size, info),
+                  "sepvad_stoi_filter")
     return taps, (info[0], info[1]), np.array(info[4:34], np.int32).reshape(15, 2)
 
 
@@ -170,18 +156,16 @@ def stoi_pairs(X, Y, fs_sig, xidx=None, yidx=None):
     N = X.shape[1]
     R = len(xidx) if xidx is not None else X.shape[0]
     dev = X.device
-    nbytes = lib.sepvad_stoi_scratch_bytes(R, N, int(fs_sig))
-    if nbytes < 0:
-        _native._check(int(nbytes), "sepvad_stoi_scratch_bytes")
-    scratch = _stoi_scratch_for(dev, nbytes)
+    scratch = _native.scratch(dev, _native.query_bytes(lib.sepvad_stoi_scratch_bytes, "sepvad_stoi_scratch_bytes",
+                                                       R, N, int(fs_sig)))
     out = torch.empty(R, device=dev, dtype=torch.float64)
     frames = torch.empty(R, device=dev, dtype=torch.int32)
     xi = torch.as_tensor(xidx, dtype=torch.int32, device=dev) if xidx is not None else None
     yi = torch.as_tensor(yidx, dtype=torch.int32, device=dev) if yidx is not None else None
-    rc = lib.sepvad_stoi(_native._ptr(X), X.shape[1], _native._ptr(Y), Y.shape[1], N, R, _native._ptr(xi),
-                         _native._ptr(yi), int(fs_sig), _native._ptr(scratch), scratch.numel(), _native._ptr(out),
-                         _native._ptr(frames), torch.cuda.current_stream(dev).cuda_stream)
-    _native._check(rc, "sepvad_stoi")
+    rc = lib.sepvad_stoi(_native.ptr(X), X.shape[1], _native.ptr(Y), Y.shape[1], N, R, _native.ptr(xi),
+                         _native.ptr(yi), int(fs_sig), _native.ptr(scratch), scratch.numel(), _native.ptr(out),
+                         _native.ptr(frames), _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_stoi")
     return out, frames
 
 
@@ -193,7 +177,7 @@ def stoi(x: torch.Tensor, y: torch.Tensor, fs_sig: int, extended: bool = False):
                                   "and is not provided")
     if x.shape != y.shape:
         raise RuntimeError(f"x and y should have the same length, found {tuple(x.shape)} and {tuple(y.shape)}")
-    X, Y = _rows(x), _rows(y)
+    X, Y = _as_rows(x), _as_rows(y)
     return stoi_pairs(X, Y, fs_sig)[0].reshape(x.shape[:-1])
 
 
@@ -241,9 +225,9 @@ class Accuracy_Vad(torch.nn.Module):
         tg = targets.to(torch.float32).contiguous()
         out = torch.empty(1 + S, device=preds.device, dtype=torch.float32)
         lib = _native.load_library()
-        rc = lib.sepvad_vad_accuracy(_native._ptr(work), _native._ptr(tg), B, S, T, 1, _native._ptr(out),
-                                     torch.cuda.current_stream(preds.device).cuda_stream)
-        _native._check(rc, "sepvad_vad_accuracy")
+        rc = lib.sepvad_vad_accuracy(_native.ptr(work), _native.ptr(tg), B, S, T, 1, _native.ptr(out),
+                                     _native.stream_ptr(preds.device))
+        _native.check(rc, "sepvad_vad_accuracy")
         if work is not preds:
             preds.copy_(work)
         return out[0], out[1], out[2]

@@ -22,28 +22,6 @@ PRECISIONS = {"fp32": SEPVAD_PREC_FP32, "f16x3": SEPVAD_PREC_F16X3, "f16": SEPVA
 # storage of the f16x3 weight lo plane in the fused TCN (include/sepvad.h SEPVAD_WLO_*)
 WEIGHT_LO = {"e4m3": 0, "f16": 1, "i8": 2}
 
-EXPORTED_SYMBOLS = (
-    "sepvad_create", "sepvad_reserve", "sepvad_set_precision", "sepvad_set_weight_lo", "sepvad_e4m3_encode",
-    "sepvad_forward", "sepvad_forward_strided",
-    "sepvad_forward_windows", "sepvad_pit_l1_sums", "sepvad_pit_l1_choose",
-    "sepvad_set_split", "sepvad_set_fused", "sepvad_fused_status", "sepvad_side_outputs", "sepvad_set_tcn_dump",
-    "sepvad_last_forward", "sepvad_side_outputs_of", "sepvad_release_stream", "sepvad_tcn_clock",
-    "sepvad_stft_gate_test", "sepvad_istft_pair_test",
-    "sepvad_stft", "sepvad_istft",
-    "sepvad_pit_l1", "sepvad_stream_append",
-    "sepvad_ring_push", "sepvad_pit_l1_rows_scratch_bytes", "sepvad_pit_l1_rows", "sepvad_live_stitch",
-    "sepvad_resample_filter", "sepvad_resample", "sepvad_normalize", "sepvad_si_sdr", "sepvad_vad_accuracy",
-    "sepvad_snr", "sepvad_stoi_filter", "sepvad_stoi_scratch_bytes", "sepvad_stoi",
-    "sepvad_eval_scratch_bytes", "sepvad_eval_separation", "sepvad_eval_vad",
-    "sepvad_stream_eval_scratch_bytes", "sepvad_stream_eval",
-    "sepvad_criterion_coef", "sepvad_criterion_backward",
-    "sepvad_rir_generate",
-    "sepvad_rir_jobs_prepare", "sepvad_rir_scratch_bytes", "sepvad_rir_generate_device", "sepvad_fir_convolve",
-    "sepvad_scene_mix", "sepvad_scene_targets", "sepvad_vad_frame_labels",
-    "sepvad_set_timing", "sepvad_timing", "sepvad_destroy", "sepvad_last_error", "sepvad_abi_version",
-    "sepvad_build_id",
-)
-
 
 def build_id() -> str:
     """Source hash the loaded library was built from (sepvad_build_id, include/sepvad.h)."""
@@ -93,6 +71,77 @@ class SepVadRirJob(ctypes.Structure):
 
 RIR_MAX_IMAGES = 16610600  # SEPVAD_RIR_MAX_IMAGES
 
+# The C ABI of include/sepvad.h, in the header's words: name -> (restype, argtypes). tests/test_host.py parses the
+# header and compares every return type, argument and struct field with this table and the classes above.
+P, i32, i64, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+_i32p, _i64p, _dblp = ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(dbl)
+_outs, _kw = ctypes.POINTER(SepVadOutputs), ctypes.POINTER(SepVadInferKw)
+_ABI = {
+    "sepvad_create": (P, (ctypes.POINTER(SepVadConfig), ctypes.POINTER(P), ctypes.POINTER(ctypes.c_char_p), _i64p, i32,
+                          i32)),
+    "sepvad_reserve": (i32, (P, i32, i32)),
+    "sepvad_set_precision": (i32, (P, i32)),
+    "sepvad_set_weight_lo": (i32, (P, i32)),
+    "sepvad_e4m3_encode": (i32, (P, P, i64)),
+    "sepvad_forward": (i32, (P, P, i32, i32, _outs, _kw, P)),
+    "sepvad_forward_strided": (i32, (P, P, i64, i32, i32, _outs, _kw, P)),
+    "sepvad_forward_windows": (i32, (P, P, i64, i32, i32, i64, i32, _outs, _kw, P)),
+    "sepvad_set_split": (i32, (P, i32)),
+    "sepvad_set_fused": (i32, (P, i32)),
+    "sepvad_fused_status": (i32, (P, _i32p)),
+    "sepvad_side_outputs": (i32, (P, _outs, P)),
+    "sepvad_last_forward": (i32, (P, P, _i64p, _i32p, _i32p)),
+    "sepvad_side_outputs_of": (i32, (P, _outs, P, i64, i32, i32)),
+    "sepvad_tcn_clock": (i32, (P, P, i32, _i32p)),
+    "sepvad_release_stream": (i32, (P, P)),
+    "sepvad_stft_gate_test": (i32, (P, P, i32, i32, P, P, P)),
+    "sepvad_istft_pair_test": (i32, (P, P, P, i32, i32, P, P, P)),
+    "sepvad_set_tcn_dump": (i32, (P, P)),
+    "sepvad_stft": (i32, (P, P, i32, i32, P, P, P)),
+    "sepvad_istft": (i32, (P, P, i32, i32, P, P)),
+    "sepvad_pit_l1": (i32, (P, i64, P, i64, i32, i64, P, P, P, P, P)),
+    "sepvad_pit_l1_sums": (i32, (P, i64, P, i64, i32, i64, P, P, P)),
+    "sepvad_pit_l1_choose": (i32, (P, dbl, i32, P, P, P, P)),
+    "sepvad_stream_append": (i32, (P, i64, i64, i32, i64, P, P, i64, i64, P)),
+    "sepvad_ring_push": (i32, (P, i64, i32, i64, P, i64, i64, P)),
+    "sepvad_pit_l1_rows_scratch_bytes": (i64, (i32, i64)),
+    "sepvad_pit_l1_rows": (i32, (P, i64, P, i64, i32, i64, P, i64, P, P, P, P)),
+    "sepvad_live_stitch": (i32, (P, i64, i64, i32, i64, P, P, i64, i64, P, i64, i64, P, i32, i32, P, i64, i64, P)),
+    "sepvad_si_sdr": (i32, (P, i64, P, i64, i64, i32, P, P, i32, P, P)),
+    "sepvad_snr": (i32, (P, i64, P, i64, i64, i32, P, P, i32, P, P)),
+    "sepvad_stoi_filter": (i32, (i32, P, i32, P)),
+    "sepvad_stoi_scratch_bytes": (i64, (i32, i64, i32)),
+    "sepvad_stoi": (i32, (P, i64, P, i64, i64, i32, P, P, i32, P, i64, P, P, P)),
+    "sepvad_vad_accuracy": (i32, (P, P, i32, i32, i32, i32, P, P)),
+    "sepvad_eval_scratch_bytes": (i64, (i32, i64)),
+    "sepvad_eval_separation": (i32, (P, i64, P, i64, P, i64, i32, i64, i32, i32, i32, dbl, P, i64, P, P, P, P, P, P)),
+    "sepvad_eval_vad": (i32, (P, P, i32, P, P, i32, i32, P, P, P, P, P, P, P)),
+    "sepvad_criterion_coef": (i32, (P, i64, P, i64, i32, i64, i32, i32, i32, dbl, P, i64, P, P, P)),
+    "sepvad_criterion_backward": (i32, (i32, P, i64, P, i64, i64, P, P, P, i64, P, P, P, i32, P, P, P)),
+    "sepvad_stream_eval_scratch_bytes": (i64, (i32, i32, i64, i64, i32)),
+    "sepvad_stream_eval": (i32, (P, i64, i32, i32, i32, i32, i64, i64, P, i64, i32, i32, i32, i32, dbl, P, i64, P, i64,
+                                 P, P, P, P, P, P, i64, P)),
+    "sepvad_rir_generate": (i32, (dbl, dbl, _dblp, i32, _dblp, _dblp, _dblp, i32, _dblp, i32, i32, i32, i32,
+                                  ctypes.c_char, _dblp, i64)),
+    "sepvad_rir_jobs_prepare": (i32, (ctypes.POINTER(SepVadRirDesc), i32, ctypes.POINTER(SepVadRirJob))),
+    "sepvad_rir_scratch_bytes": (i64, (i32, i64)),
+    "sepvad_rir_generate_device": (i32, (P, i32, P, i64, P, i64, P)),
+    "sepvad_fir_convolve": (i32, (P, i64, i64, P, i64, i32, P, P, P, i32, i64, P, i64, P)),
+    "sepvad_scene_mix": (i32, (P, i32, i32, i64, P, P, i32, dbl, dbl, P, P, P)),
+    "sepvad_scene_targets": (i32, (P, i32, i32, i64, i32, dbl, dbl, P, P, P)),
+    "sepvad_vad_frame_labels": (i32, (P, i64, i32, i64, i32, P, P)),
+    "sepvad_resample_filter": (i32, (i32, i32, P, i32, P)),
+    "sepvad_resample": (i32, (P, i64, P, P, P, i64, P)),
+    "sepvad_normalize": (i32, (P, i64, P, P, P)),
+    "sepvad_set_timing": (i32, (P, i32)),
+    "sepvad_timing": (i32, (P, _dblp, _i32p, _dblp)),
+    "sepvad_destroy": (None, (P,)),
+    "sepvad_last_error": (ctypes.c_char_p, ()),
+    "sepvad_abi_version": (i32, ()),
+    "sepvad_build_id": (ctypes.c_char_p, ()),
+}
+EXPORTED_SYMBOLS = tuple(_ABI)
+
 _lib = None
 
 # SEPVAD_CHECK=1: synchronise after every forward and raise if its fused TCN hand-offs gave up. Without it
@@ -110,143 +159,91 @@ def load_library(path: str = LIB_PATH):
         raise RuntimeError(f"libsepvad.so not found at {path}: build it with `python -c 'import __graft_entry__ as g; "
                            f"g.build()'` or `make -C sep-tfanet-vad_amd/csrc`")
     lib = ctypes.CDLL(path)
-    P = ctypes.c_void_p
-    i32 = ctypes.c_int32
-    lib.sepvad_create.restype = P
-    lib.sepvad_create.argtypes = [ctypes.POINTER(SepVadConfig), ctypes.POINTER(P), ctypes.POINTER(ctypes.c_char_p),
-                                  ctypes.POINTER(ctypes.c_int64), i32, i32]
-    lib.sepvad_reserve.restype = i32
-    lib.sepvad_reserve.argtypes = [P, i32, i32]
-    lib.sepvad_set_precision.restype = i32
-    lib.sepvad_set_precision.argtypes = [P, i32]
-    lib.sepvad_set_weight_lo.restype = i32
-    lib.sepvad_set_weight_lo.argtypes = [P, i32]
-    lib.sepvad_e4m3_encode.restype = i32
-    lib.sepvad_e4m3_encode.argtypes = [P, P, ctypes.c_int64]
-    lib.sepvad_forward.restype = i32
-    lib.sepvad_forward.argtypes = [P, P, i32, i32, ctypes.POINTER(SepVadOutputs), ctypes.POINTER(SepVadInferKw), P]
-    lib.sepvad_forward_strided.restype = i32
-    lib.sepvad_forward_strided.argtypes = [P, P, ctypes.c_int64, i32, i32, ctypes.POINTER(SepVadOutputs),
-                                           ctypes.POINTER(SepVadInferKw), P]
-    lib.sepvad_forward_windows.restype = i32
-    lib.sepvad_forward_windows.argtypes = [P, P, ctypes.c_int64, i32, i32, ctypes.c_int64, i32,
-                                           ctypes.POINTER(SepVadOutputs), ctypes.POINTER(SepVadInferKw), P]
-    lib.sepvad_pit_l1_sums.restype = i32
-    lib.sepvad_pit_l1_sums.argtypes = [P, ctypes.c_int64, P, ctypes.c_int64, i32, ctypes.c_int64, P, P, P]
-    lib.sepvad_pit_l1_choose.restype = i32
-    lib.sepvad_pit_l1_choose.argtypes = [P, ctypes.c_double, i32, P, P, P, P]
-    lib.sepvad_set_split.restype = i32
-    lib.sepvad_set_split.argtypes = [P, i32]
-    lib.sepvad_set_fused.restype = i32
-    lib.sepvad_set_fused.argtypes = [P, i32]
-    lib.sepvad_fused_status.restype = i32
-    lib.sepvad_fused_status.argtypes = [P, ctypes.POINTER(i32)]
-    lib.sepvad_set_tcn_dump.restype = i32
-    lib.sepvad_set_tcn_dump.argtypes = [P, P]
-    lib.sepvad_side_outputs.restype = i32
-    lib.sepvad_side_outputs.argtypes = [P, ctypes.POINTER(SepVadOutputs), P]
-    lib.sepvad_last_forward.restype = i32
-    lib.sepvad_last_forward.argtypes = [P, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    lib.sepvad_side_outputs_of.restype = i32
-    lib.sepvad_side_outputs_of.argtypes = [P, ctypes.POINTER(SepVadOutputs), P, ctypes.c_int64, i32, i32]
-    lib.sepvad_release_stream.restype = i32
-    lib.sepvad_release_stream.argtypes = [P, P]
-    lib.sepvad_tcn_clock.restype = i32
-    lib.sepvad_tcn_clock.argtypes = [P, P, i32, ctypes.POINTER(i32)]
-    lib.sepvad_stft_gate_test.restype = i32
-    lib.sepvad_stft_gate_test.argtypes = [P, P, i32, i32, P, P, P]
-    lib.sepvad_istft_pair_test.restype = i32
-    lib.sepvad_istft_pair_test.argtypes = [P, P, P, i32, i32, P, P, P]
-    lib.sepvad_stft.restype = i32
-    lib.sepvad_stft.argtypes = [P, P, i32, i32, P, P, P]
-    lib.sepvad_istft.restype = i32
-    lib.sepvad_istft.argtypes = [P, P, i32, i32, P, P]
-    i64 = ctypes.c_int64
-    lib.sepvad_pit_l1.restype = i32
-    lib.sepvad_pit_l1.argtypes = [P, i64, P, i64, i32, i64, P, P, P, P, P]
-    lib.sepvad_stream_append.restype = i32
-    lib.sepvad_stream_append.argtypes = [P, i64, i64, i32, i64, P, P, i64, i64, P]
-    lib.sepvad_ring_push.restype = i32
-    lib.sepvad_ring_push.argtypes = [P, i64, i32, i64, P, i64, i64, P]
-    lib.sepvad_pit_l1_rows_scratch_bytes.restype = i64
-    lib.sepvad_pit_l1_rows_scratch_bytes.argtypes = [i32, i64]
-    lib.sepvad_pit_l1_rows.restype = i32
-    lib.sepvad_pit_l1_rows.argtypes = [P, i64, P, i64, i32, i64, P, i64, P, P, P, P]
-    lib.sepvad_live_stitch.restype = i32
-    lib.sepvad_live_stitch.argtypes = [P, i64, i64, i32, i64, P, P, i64, i64, P, i64, i64, P, i32, i32, P, i64, i64, P]
-    lib.sepvad_resample_filter.restype = i32
-    lib.sepvad_resample_filter.argtypes = [i32, i32, P, i32, P]
-    lib.sepvad_resample.restype = i32
-    lib.sepvad_resample.argtypes = [P, i64, P, P, P, i64, P]
-    lib.sepvad_normalize.restype = i32
-    lib.sepvad_normalize.argtypes = [P, i64, P, P, P]
-    lib.sepvad_si_sdr.restype = i32
-    lib.sepvad_si_sdr.argtypes = [P, i64, P, i64, i64, i32, P, P, i32, P, P]
-    lib.sepvad_snr.restype = i32
-    lib.sepvad_snr.argtypes = [P, i64, P, i64, i64, i32, P, P, i32, P, P]
-    lib.sepvad_stoi_filter.restype = i32
-    lib.sepvad_stoi_filter.argtypes = [i32, P, i32, P]
-    lib.sepvad_stoi_scratch_bytes.restype = i64
-    lib.sepvad_stoi_scratch_bytes.argtypes = [i32, i64, i32]
-    lib.sepvad_stoi.restype = i32
-    lib.sepvad_stoi.argtypes = [P, i64, P, i64, i64, i32, P, P, i32, P, i64, P, P, P]
-    lib.sepvad_vad_accuracy.restype = i32
-    lib.sepvad_vad_accuracy.argtypes = [P, P, i32, i32, i32, i32, P, P]
-    lib.sepvad_eval_scratch_bytes.restype = i64
-    lib.sepvad_eval_scratch_bytes.argtypes = [i32, i64]
-    lib.sepvad_eval_separation.restype = i32
-    lib.sepvad_eval_separation.argtypes = [P, i64, P, i64, P, i64, i32, i64, i32, i32, i32, ctypes.c_double, P, i64,
-                                           P, P, P, P, P, P]
-    lib.sepvad_eval_vad.restype = i32
-    lib.sepvad_eval_vad.argtypes = [P, P, i32, P, P, i32, i32, P, P, P, P, P, P, P]
-    lib.sepvad_stream_eval_scratch_bytes.restype = i64
-    lib.sepvad_stream_eval_scratch_bytes.argtypes = [i32, i32, i64, i64, i32]
-    lib.sepvad_stream_eval.restype = i32
-    lib.sepvad_stream_eval.argtypes = [P, i64, i32, i32, i32, i32, i64, i64, P, i64, i32, i32, i32, i32, ctypes.c_double,
-                                       P, i64, P, i64, P, P, P, P, P, P, i64, P]
-    lib.sepvad_criterion_coef.restype = i32
-    lib.sepvad_criterion_coef.argtypes = [P, i64, P, i64, i32, i64, i32, i32, i32, ctypes.c_double, P, i64, P, P, P]
-    lib.sepvad_criterion_backward.restype = i32
-    lib.sepvad_criterion_backward.argtypes = [i32, P, i64, P, i64, i64, P, P, P, i64, P, P, P, i32, P, P, P]
-    dptr = ctypes.POINTER(ctypes.c_double)
-    lib.sepvad_rir_generate.restype = i32
-    lib.sepvad_rir_generate.argtypes = [ctypes.c_double, ctypes.c_double, dptr, i32, dptr, dptr, dptr, i32, dptr,
-                                        i32, i32, i32, i32, ctypes.c_char, dptr, i64]
-    dbl = ctypes.c_double
-    lib.sepvad_rir_jobs_prepare.restype = i32
-    lib.sepvad_rir_jobs_prepare.argtypes = [ctypes.POINTER(SepVadRirDesc), i32, ctypes.POINTER(SepVadRirJob)]
-    lib.sepvad_rir_scratch_bytes.restype = i64
-    lib.sepvad_rir_scratch_bytes.argtypes = [i32, i64]
-    lib.sepvad_rir_generate_device.restype = i32
-    lib.sepvad_rir_generate_device.argtypes = [P, i32, P, i64, P, i64, P]
-    lib.sepvad_fir_convolve.restype = i32
-    lib.sepvad_fir_convolve.argtypes = [P, i64, i64, P, i64, i32, P, P, P, i32, i64, P, i64, P]
-    lib.sepvad_scene_mix.restype = i32
-    lib.sepvad_scene_mix.argtypes = [P, i32, i32, i64, P, P, i32, dbl, dbl, P, P, P]
-    lib.sepvad_scene_targets.restype = i32
-    lib.sepvad_scene_targets.argtypes = [P, i32, i32, i64, i32, dbl, dbl, P, P, P]
-    lib.sepvad_vad_frame_labels.restype = i32
-    lib.sepvad_vad_frame_labels.argtypes = [P, i64, i32, i64, i32, P, P]
-    lib.sepvad_set_timing.restype = i32
-    lib.sepvad_set_timing.argtypes = [P, i32]
-    lib.sepvad_timing.restype = i32
-    lib.sepvad_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double)]
-    lib.sepvad_destroy.restype = None
-    lib.sepvad_destroy.argtypes = [P]
-    lib.sepvad_last_error.restype = ctypes.c_char_p
-    lib.sepvad_last_error.argtypes = []
-    lib.sepvad_abi_version.restype = i32
-    lib.sepvad_abi_version.argtypes = []
-    lib.sepvad_build_id.restype = ctypes.c_char_p
-    lib.sepvad_build_id.argtypes = []
+    for name, (restype, argtypes) in _ABI.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = lib
     return lib
 
 
-def _check(rc, what):
+def check(rc, what):
     if rc != 0:
         msg = _lib.sepvad_last_error().decode(errors="replace")
         raise RuntimeError(f"{what} failed (status {rc}): {msg}")
+
+
+def ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+_check, _ptr = check, ptr  # the names older callers use
+
+
+# ---- glue between torch tensors and the entries: every wrapper module takes these from here ----------------------
+def stream_ptr(device):
+    """The current stream of `device` as the entries' hipStream_t argument."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+_scratch = {}  # (device, stream) -> uint8 scratch, most recently used last
+
+
+def scratch(device, nbytes):
+    """At least nbytes of scratch for the current stream on `device` (one buffer per stream: concurrent streams never
+    share it). The entries consume their scratch within their own stream-ordered launches, so PIT, evaluation and STOI
+    share it; a caller that reads it across two entries keeps the returned tensor (eval_separation's "scratch")."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    buf = _scratch.pop(key, None)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        while len(_scratch) >= 32:  # bounded: drop the least recently used stream's scratch (its blocks return
+            _scratch.pop(next(iter(_scratch)))  # to that stream's allocator pool, reused only in its order)
+    _scratch[key] = buf
+    return buf
+
+
+def query_bytes(fn, what, *args):
+    """A host size query (sepvad_*_scratch_bytes): its answer, or the error of its negative status."""
+    nbytes = fn(*args)
+    if nbytes < 0:
+        check(nbytes, what)
+    return nbytes
+
+
+def rows3(t):
+    """[B, 2, N] float32 with unit sample stride, speaker stride ld >= N and batch stride 2 ld -> (tensor, ld).
+    One shape and one stride query: this runs for every window of the streaming wrappers."""
+    shape = t.shape
+    if len(shape) != 3 or shape[1] != 2:
+        raise ValueError(f"expected [B, 2, L], got {tuple(shape)}")
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    s0, s1, s2 = t.stride()
+    if s2 != 1 or s1 < shape[2] or (shape[0] > 1 and s0 != 2 * s1):
+        t = t.contiguous()
+        s1 = t.stride(1)
+    return t, s1
+
+
+def rows2(t):
+    """[B, N] float32 with unit sample stride and row stride ld >= N -> (tensor, ld)."""
+    B, N = t.shape
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    s0, s1 = t.stride()
+    if s1 != 1 or (B > 1 and s0 < N):
+        t = t.contiguous()
+        s0 = t.stride(0)
+    return t, (s0 if B > 1 else N)
+
+
+def require_device(what, first, *rest):
+    if first.device.type != "cuda":
+        raise RuntimeError(f"{what}: inputs must be ROCm device tensors")
+    for t in rest:
+        if t is not None and t.device != first.device:
+            raise RuntimeError(f"{what}: inputs must be on one ROCm device")
+    return first.device
 
 
 def make_config(cfg: dict, precision: str = "f16x3") -> SepVadConfig:
@@ -277,10 +274,6 @@ def make_kw(inference_kw) -> SepVadInferKw | None:
     k.threshold_activated_vad = float(inference_kw["threshold_activated_vad"])
     k.return_smoothed_vad = int(bool(inference_kw["return_smoothed_vad"]))
     return k
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 class Handle:
@@ -364,7 +357,7 @@ class Handle:
         return dict(gemm_ms=ms[0], res_out_ms=ms[1], gemm_launches=cnt[0], res_out_launches=cnt[1], total_ms=tot.value)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream_ptr(self.device)
 
     def forward(self, x: torch.Tensor, inference_kw=None, return_aux: bool = False, outputs: dict | None = None):
         """One forward. Returns dict(sep, vad, est[, spectrum, masks_b, mask_per_speaker])."""

@@ -34,8 +34,6 @@ Deliberate differences from the reference:
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 from torch import nn
@@ -47,29 +45,21 @@ from .online import MAX_WINDOW_UTTS, _slice_bounds
 SE_NONE, SE_L1, SE_SISDR = 0, 1, 2  # SEPVAD_SE_* (include/sepvad.h)
 
 
-def _rows3(t):
-    """[B, 2, N] float32 with unit sample stride and batch stride 2 x speaker stride -> (tensor, ld)."""
-    t = t.to(torch.float32)
-    if t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) != 2 * t.stride(1):
-        t = t.contiguous()
-    return t, t.stride(1)
-
-
 def sisdr_under_perm(est, tgt, perm):
     """calc_sisdr(reorder_source_mse(est, perm), tgt) -> [B, 2] (model/combined_loss.py:16-56,63-78) without the
     reordered copy: ``sepvad_si_sdr`` reads the strided rows through index arrays built on the device."""
     lib = _native.load_library()
-    est, eld = _rows3(est)
-    tgt, tld = _rows3(tgt)
+    est, eld = _native.rows3(est)
+    tgt, tld = _native.rows3(tgt)
     B, _, N = est.shape
     dev = est.device
     rows = torch.arange(2 * B, device=dev, dtype=torch.int64)
     pidx = ((rows >> 1) * 2 + perm.reshape(-1)).to(torch.int32)
     tidx = rows.to(torch.int32)
     out = torch.empty(2 * B, device=dev, dtype=torch.float32)
-    rc = lib.sepvad_si_sdr(_native._ptr(est), eld, _native._ptr(tgt), tld, N, 2 * B, _native._ptr(pidx),
-                           _native._ptr(tidx), 1, _native._ptr(out), torch.cuda.current_stream(dev).cuda_stream)
-    _native._check(rc, "sepvad_si_sdr")
+    rc = lib.sepvad_si_sdr(_native.ptr(est), eld, _native.ptr(tgt), tld, N, 2 * B, _native.ptr(pidx),
+                           _native.ptr(tidx), 1, _native.ptr(out), _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_si_sdr")
     return out.reshape(B, 2)
 
 
@@ -82,7 +72,7 @@ class StreamEval:
     def __init__(self, tgt, K, W, H, mode, sdr_type="sisdr", zero_mean=True, take_log=True, eps=1e-8):
         from .evaluate import SDR_TYPES
         self.lib = _native.load_library()
-        self.tgt, self.tgt_ld = _rows3(tgt)
+        self.tgt, self.tgt_ld = _native.rows3(tgt)
         self.B, self.K, self.W, self.H, self.mode = self.tgt.shape[0], int(K), int(W), int(H), int(mode)
         self.crit = (SDR_TYPES[sdr_type], int(bool(zero_mean)), int(bool(take_log)), float(eps))
         dev, B = self.tgt.device, self.B
@@ -101,19 +91,17 @@ class StreamEval:
         if tuple(sep_w.shape[1:]) != (self.B, 2, self.W) or sep_w.dtype != torch.float32 or not sep_w.is_contiguous():
             raise ValueError(f"StreamEval.push: expected contiguous float32 [n, {self.B}, 2, {self.W}], got "
                              f"{tuple(sep_w.shape)}")
-        nbytes = int(self.lib.sepvad_stream_eval_scratch_bytes(self.B, n, self.W, self.H, self.mode))
-        if nbytes < 0:
-            _native._check(nbytes, "sepvad_stream_eval_scratch_bytes")
+        nbytes = _native.query_bytes(self.lib.sepvad_stream_eval_scratch_bytes, "sepvad_stream_eval_scratch_bytes",
+                                     self.B, n, self.W, self.H, self.mode)
         if self.scratch is None or self.scratch.numel() * 8 < nbytes:
             self.scratch = torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.float64, device=sep_w.device)
-        P = _native._ptr
+        P = _native.ptr
         rc = self.lib.sepvad_stream_eval(
             P(sep_w), self.W, n, int(k0), self.K, self.B, self.W, self.H, P(self.tgt), self.tgt_ld, self.mode,
             *self.crit, P(self.raw), self.raw.stride(1), P(self.online), self.online.stride(1), P(self.perm),
             P(self.perm_tgt) if self.mode != SE_NONE else None, P(self.pw_tgt), P(self.loss_tgt), P(self.pw_sim),
-            P(self.scratch), self.scratch.numel() * 8,
-            ctypes.c_void_p(torch.cuda.current_stream(sep_w.device).cuda_stream))
-        _native._check(rc, "sepvad_stream_eval")
+            P(self.scratch), self.scratch.numel() * 8, _native.stream_ptr(sep_w.device))
+        _native.check(rc, "sepvad_stream_eval")
 
 
 class OnlineSaving:

@@ -16,41 +16,12 @@ same scalar and the chosen permutation is shared by the whole batch.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 
 from . import native as _native
 
 PIT_SCRATCH_BYTES = 16448  # SEPVAD_PIT_SCRATCH_BYTES (include/sepvad.h)
-_scratch = {}
-
-
-def _scratch_for(device):
-    """Scratch of the current stream on `device` (one per stream: concurrent streams never share it)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    buf = _scratch.pop(key, None)
-    if buf is None:
-        buf = torch.empty(PIT_SCRATCH_BYTES // 8, dtype=torch.float64, device=device)
-        while len(_scratch) >= 32:  # bounded: drop the least recently used stream's scratch (its blocks return
-            _scratch.pop(next(iter(_scratch)))  # to that stream's allocator pool, reused only in its order)
-    _scratch[key] = buf  # most recently used last
-    return buf
-
-
-def _rows(t: torch.Tensor):
-    """[B, 2, L] view with unit sample stride and a common speaker/batch row stride -> (ptr, ld)."""
-    if t.dim() != 3 or t.shape[1] != 2:
-        raise ValueError(f"expected [B, 2, L], got {tuple(t.shape)}")
-    if t.stride(2) != 1 or t.stride(0) != 2 * t.stride(1):
-        t = t.contiguous()
-    return t, t.stride(1)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
 
 def pit_l1(est: torch.Tensor, ref: torch.Tensor):
     """(min loss [scalar], batch_indices [B, 2] int64, pairwise [2, 2]) on the device."""
@@ -59,18 +30,17 @@ def pit_l1(est: torch.Tensor, ref: torch.Tensor):
         raise RuntimeError("pit_l1: est and ref must be on the same ROCm device")
     if est.shape != ref.shape:
         raise ValueError(f"pit_l1: shape mismatch {tuple(est.shape)} vs {tuple(ref.shape)}")
-    est = est.float()
-    ref = ref.float()
-    est, eld = _rows(est)
-    ref, rld = _rows(ref)
+    est, eld = _native.rows3(est)
+    ref, rld = _native.rows3(ref)
     B, _, L = est.shape
     dev = est.device
     perm = torch.empty(B, 2, dtype=torch.int64, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     pw = torch.empty(2, 2, dtype=torch.float32, device=dev)
-    rc = lib.sepvad_pit_l1(_native._ptr(est), eld, _native._ptr(ref), rld, B, L, _native._ptr(_scratch_for(dev)),
-                           _native._ptr(perm), _native._ptr(loss), _native._ptr(pw), _stream(dev))
-    _native._check(rc, "sepvad_pit_l1")
+    scratch = _native.scratch(dev, PIT_SCRATCH_BYTES)
+    rc = lib.sepvad_pit_l1(_native.ptr(est), eld, _native.ptr(ref), rld, B, L, _native.ptr(scratch),
+                           _native.ptr(perm), _native.ptr(loss), _native.ptr(pw), _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_pit_l1")
     return loss, perm, pw
 
 
@@ -83,20 +53,18 @@ def pit_l1_rows(est: torch.Tensor, ref: torch.Tensor):
         raise RuntimeError("pit_l1_rows: est and ref must be on the same ROCm device")
     if est.shape != ref.shape:
         raise ValueError(f"pit_l1_rows: shape mismatch {tuple(est.shape)} vs {tuple(ref.shape)}")
-    est, eld = _rows(est.float())
-    ref, rld = _rows(ref.float())
+    est, eld = _native.rows3(est)
+    ref, rld = _native.rows3(ref)
     B, _, L = est.shape
     dev = est.device
-    nbytes = int(lib.sepvad_pit_l1_rows_scratch_bytes(B, L))
-    if nbytes < 0:
-        _native._check(nbytes, "sepvad_pit_l1_rows_scratch_bytes")
+    nbytes = _native.query_bytes(lib.sepvad_pit_l1_rows_scratch_bytes, "sepvad_pit_l1_rows_scratch_bytes", B, L)
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     perm = torch.empty(B, 2, dtype=torch.int64, device=dev)
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     pw = torch.empty(B, 2, 2, dtype=torch.float32, device=dev)
-    rc = lib.sepvad_pit_l1_rows(_native._ptr(est), eld, _native._ptr(ref), rld, B, L, _native._ptr(scratch), nbytes,
-                                _native._ptr(perm), _native._ptr(loss), _native._ptr(pw), _stream(dev))
-    _native._check(rc, "sepvad_pit_l1_rows")
+    rc = lib.sepvad_pit_l1_rows(_native.ptr(est), eld, _native.ptr(ref), rld, B, L, _native.ptr(scratch), nbytes,
+                                _native.ptr(perm), _native.ptr(loss), _native.ptr(pw), _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_pit_l1_rows")
     return loss, perm, pw
 
 
@@ -107,14 +75,15 @@ def pit_l1_sharded(est: torch.Tensor, ref: torch.Tensor, total_rows: int, group=
     (sepvad_pit_l1_choose) with count = total_rows * L."""
     import torch.distributed as dist
     lib = _native.load_library()
-    est, eld = _rows(est.float())
-    ref, rld = _rows(ref.float())
+    est, eld = _native.rows3(est)
+    ref, rld = _native.rows3(ref)
     B, _, L = est.shape
     dev = est.device
     buf = torch.empty(4, dtype=torch.float64, device=dev)
-    rc = lib.sepvad_pit_l1_sums(_native._ptr(est), eld, _native._ptr(ref), rld, B, L, _native._ptr(_scratch_for(dev)),
-                                _native._ptr(buf), _stream(dev))
-    _native._check(rc, "sepvad_pit_l1_sums")
+    scratch = _native.scratch(dev, PIT_SCRATCH_BYTES)
+    rc = lib.sepvad_pit_l1_sums(_native.ptr(est), eld, _native.ptr(ref), rld, B, L, _native.ptr(scratch),
+                                _native.ptr(buf), _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_pit_l1_sums")
     if dist.get_backend(group) == "gloo":  # (tests on a shared GPU: gloo reduces host tensors)
         hb = buf.cpu()
         dist.all_reduce(hb, op=dist.ReduceOp.SUM, group=group)
@@ -125,9 +94,9 @@ def pit_l1_sharded(est: torch.Tensor, ref: torch.Tensor, total_rows: int, group=
     perm = torch.empty(B, 2, dtype=torch.int64, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     pw = torch.empty(2, 2, dtype=torch.float32, device=dev)
-    rc = lib.sepvad_pit_l1_choose(_native._ptr(buf), count, B, _native._ptr(perm), _native._ptr(loss), _native._ptr(pw),
-                                  _stream(dev))
-    _native._check(rc, "sepvad_pit_l1_choose")
+    rc = lib.sepvad_pit_l1_choose(_native.ptr(buf), count, B, _native.ptr(perm), _native.ptr(loss), _native.ptr(pw),
+                                  _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_pit_l1_choose")
     return loss, perm, pw
 
 
@@ -156,7 +125,7 @@ def pit_sisdr_rows(est: torch.Tensor, ref: torch.Tensor):
 def stream_append(src: torch.Tensor, s0: int, H: int, perm, dst: torch.Tensor, d0: int):
     """dst[b, i, d0:d0+H] = src[b, perm[b, i], s0:s0+H] (perm None = identity), on the device."""
     lib = _native.load_library()
-    src, sld = _rows(src)
+    src, sld = _native.rows3(src)
     if dst.dim() != 3 or dst.stride(2) != 1 or dst.stride(0) != 2 * dst.stride(1):
         raise ValueError("stream_append: dst must be a [B, 2, L] buffer with unit sample stride")
     B = src.shape[0]
@@ -164,10 +133,10 @@ def stream_append(src: torch.Tensor, s0: int, H: int, perm, dst: torch.Tensor, d
         perm = perm.to(device=src.device, dtype=torch.int64).contiguous()
         if tuple(perm.shape) != (B, 2):
             raise ValueError("stream_append: perm must be [B, 2]")
-    rc = lib.sepvad_stream_append(_native._ptr(src), sld, int(s0), B, int(H),
-                                  _native._ptr(perm) if perm is not None else None,
-                                  _native._ptr(dst), dst.stride(1), int(d0), _stream(src.device))
-    _native._check(rc, "sepvad_stream_append")
+    rc = lib.sepvad_stream_append(_native.ptr(src), sld, int(s0), B, int(H),
+                                  _native.ptr(perm) if perm is not None else None,
+                                  _native.ptr(dst), dst.stride(1), int(d0), _native.stream_ptr(src.device))
+    _native.check(rc, "sepvad_stream_append")
 
 
 def reorder_source_mse(preds: torch.Tensor, batch_indices: torch.Tensor) -> torch.Tensor:

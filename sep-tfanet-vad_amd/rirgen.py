@@ -109,8 +109,8 @@ def generateRirBatch(jobs, device="cuda", ld=None):  # noqa: N802
         lib = _native.load_library()
         if lib.sepvad_rir_scratch_bytes(J, ld) < 0:
             raise RuntimeError("sepvad_rir_scratch_bytes failed")
-        _native._check(lib.sepvad_rir_generate_device(_native._ptr(tab), J, _native._ptr(h), ld, None, 0,
-                                                      torch.cuda.current_stream(device).cuda_stream),
+        _native.check(lib.sepvad_rir_generate_device(_native.ptr(tab), J, _native.ptr(h), ld, None, 0,
+                                                      _native.stream_ptr(device)),
                        "sepvad_rir_generate_device")
         klen = torch.tensor(lens, dtype=torch.int32).to(device)
     return h, klen

@@ -14,10 +14,6 @@ from . import native as _native
 from . import rirgen as _rirgen
 
 
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _need(t, dtype, what):
     if t.device.type != "cuda" or t.dtype != dtype:
         raise RuntimeError(f"{what} must be a {dtype} ROCm tensor")
@@ -37,9 +33,10 @@ def fir_convolve(x, h, L, klen=None, xidx=None, hidx=None):
             _need(t, torch.int32, "fir_convolve: " + n)
     y = torch.empty(R, int(L), device=x.device, dtype=torch.float64)
     lib = _native.load_library()
-    _native._check(lib.sepvad_fir_convolve(_native._ptr(x), x.shape[1], x.shape[1], _native._ptr(h), h.shape[1],
-                                           h.shape[1], _native._ptr(klen), _native._ptr(xidx), _native._ptr(hidx), R,
-                                           int(L), _native._ptr(y), int(L), _stream(x.device)), "sepvad_fir_convolve")
+    _native.check(lib.sepvad_fir_convolve(_native.ptr(x), x.shape[1], x.shape[1], _native.ptr(h), h.shape[1],
+                                           h.shape[1], _native.ptr(klen), _native.ptr(xidx), _native.ptr(hidx), R,
+                                           int(L), _native.ptr(y), int(L), _native.stream_ptr(x.device)),
+                  "sepvad_fir_convolve")
     return y
 
 
@@ -57,9 +54,9 @@ def scene_mix(rev, noise=None, snr_db=None, a=1.8, b=0.9, power_mode=0):
     mix = torch.empty(B, L, device=rev.device, dtype=torch.float32)
     stats = torch.empty(B, 4, device=rev.device, dtype=torch.float64)
     lib = _native.load_library()
-    _native._check(lib.sepvad_scene_mix(_native._ptr(rev), B, S, L, _native._ptr(noise), _native._ptr(snr_db),
-                                        int(power_mode), float(a), float(b), _native._ptr(mix), _native._ptr(stats),
-                                        _stream(rev.device)), "sepvad_scene_mix")
+    _native.check(lib.sepvad_scene_mix(_native.ptr(rev), B, S, L, _native.ptr(noise), _native.ptr(snr_db),
+                                        int(power_mode), float(a), float(b), _native.ptr(mix), _native.ptr(stats),
+                                        _native.stream_ptr(rev.device)), "sepvad_scene_mix")
     return mix, stats
 
 
@@ -71,8 +68,8 @@ def scene_targets(dry, stats=None, mode=1, a=1.8, b=0.9):
         stats = _need(stats, torch.float64, "scene_targets: stats")
     out = torch.empty(B, S, L, device=dry.device, dtype=torch.float32)
     lib = _native.load_library()
-    _native._check(lib.sepvad_scene_targets(_native._ptr(dry), B, S, L, int(mode), float(a), float(b),
-                                            _native._ptr(stats), _native._ptr(out), _stream(dry.device)),
+    _native.check(lib.sepvad_scene_targets(_native.ptr(dry), B, S, L, int(mode), float(a), float(b),
+                                            _native.ptr(stats), _native.ptr(out), _native.stream_ptr(dry.device)),
                    "sepvad_scene_targets")
     return out
 
@@ -85,8 +82,9 @@ def vad_frame_labels(act, edge_mode=0):
     T = 2 * L // 512 + 1
     out = torch.empty(rows.shape[0], T, device=act.device, dtype=torch.float32)
     lib = _native.load_library()
-    _native._check(lib.sepvad_vad_frame_labels(_native._ptr(rows), L, rows.shape[0], L, int(edge_mode),
-                                               _native._ptr(out), _stream(act.device)), "sepvad_vad_frame_labels")
+    _native.check(lib.sepvad_vad_frame_labels(_native.ptr(rows), L, rows.shape[0], L, int(edge_mode),
+                                               _native.ptr(out), _native.stream_ptr(act.device)),
+                  "sepvad_vad_frame_labels")
     return out.reshape(*act.shape[:-1], T)
 
 

@@ -36,19 +36,17 @@ class _Criterion(torch.autograd.Function):
         lib = _native.load_library()
         dev = est.device
         ctx.est_meta, ctx.vad_meta = (est.dtype, est.shape), None
-        est, eld = _evaluate._rows3(est.detach())
-        tgt, tld = _evaluate._rows3(tgt)
+        est, eld = _native.rows3(est.detach())
+        tgt, tld = _native.rows3(tgt)
         B, _, N = est.shape
         r = _evaluate.eval_separation(est, tgt, None, sdr_type, zero_mean, take_log, eps, sheet=False)
-        perm = r["perm"]
-        # the moments' partials are still in the stream's scratch (nothing ran on it since)
-        scratch = _evaluate._scratch_for(dev, int(lib.sepvad_eval_scratch_bytes(B, N)))
+        perm, scratch = r["perm"], r["scratch"]  # the moments' partials are in the buffer that call used
         coef = torch.empty(B, 2, CRIT_COEF, dtype=torch.float64, device=dev)
-        rc = lib.sepvad_criterion_coef(_native._ptr(est), eld, _native._ptr(tgt), tld, B, N,
+        rc = lib.sepvad_criterion_coef(_native.ptr(est), eld, _native.ptr(tgt), tld, B, N,
                                        _evaluate.SDR_TYPES[sdr_type], int(bool(zero_mean)), int(bool(take_log)),
-                                       float(eps), _native._ptr(scratch), scratch.numel() * 8, _native._ptr(perm),
-                                       _native._ptr(coef), _evaluate._stream(dev))
-        _native._check(rc, "sepvad_criterion_coef")
+                                       float(eps), _native.ptr(scratch), scratch.numel(), _native.ptr(perm),
+                                       _native.ptr(coef), _native.stream_ptr(dev))
+        _native.check(rc, "sepvad_criterion_coef")
         vad_loss = v32 = lab = None
         if vad is not None:
             ctx.vad_meta = (vad.dtype, vad.shape)
@@ -80,11 +78,11 @@ class _Criterion(torch.autograd.Function):
         if want_sep or want_vad:
             none = None
             rc = lib.sepvad_criterion_backward(
-                B, _native._ptr(est if want_sep else none), est.stride(1), _native._ptr(tgt), tgt.stride(1), N,
-                _native._ptr(coef), _native._ptr(g_sep if want_sep else none), _native._ptr(grad_est), N,
-                _native._ptr(vad if want_vad else none), _native._ptr(lab), _native._ptr(perm), T,
-                _native._ptr(g_vad if want_vad else none), _native._ptr(grad_vad), _evaluate._stream(dev))
-            _native._check(rc, "sepvad_criterion_backward")
+                B, _native.ptr(est if want_sep else none), est.stride(1), _native.ptr(tgt), tgt.stride(1), N,
+                _native.ptr(coef), _native.ptr(g_sep if want_sep else none), _native.ptr(grad_est), N,
+                _native.ptr(vad if want_vad else none), _native.ptr(lab), _native.ptr(perm), T,
+                _native.ptr(g_vad if want_vad else none), _native.ptr(grad_vad), _native.stream_ptr(dev))
+            _native.check(rc, "sepvad_criterion_backward")
         if grad_est is not None:
             grad_est = grad_est.to(ctx.est_meta[0]).reshape(ctx.est_meta[1])
         if grad_vad is not None:
@@ -146,7 +144,7 @@ class CombinedLoss(nn.Module):
         if torch.is_grad_enabled() and (target_separation.requires_grad or (with_vad and target_vad.requires_grad)):
             raise RuntimeError(f"{what}: differentiable with respect to pred_separation and pred_vad only, but a "
                                "target requires grad; detach it")
-        _evaluate._device_of(what, pred_separation, target_separation, *((pred_vad, target_vad) if with_vad else ()))
+        _native.require_device(what, pred_separation, target_separation, *((pred_vad, target_vad) if with_vad else ()))
         sdr_type, zero_mean, take_log, eps = self._settings
         separation_loss, vad_loss, batch_indices_separation = _Criterion.apply(
             pred_separation, target_separation, pred_vad if with_vad else None, target_vad if with_vad else None,

@@ -173,7 +173,7 @@ def test_pit_sums_decompose_over_shards():
         part = torch.empty(4, dtype=torch.float64, device=DEV)
         e, r = est[lo:hi].contiguous(), ref[lo:hi].contiguous()
         rc = lib.sepvad_pit_l1_sums(native._ptr(e), e.stride(1), native._ptr(r), r.stride(1), hi - lo, 3000,
-                                    native._ptr(pit._scratch_for(est.device)), native._ptr(part),
+                                    native._ptr(native.scratch(est.device, pit.PIT_SCRATCH_BYTES)), native._ptr(part),
                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         native._check(rc, "sepvad_pit_l1_sums")
         sums += part

