@@ -435,6 +435,45 @@ int32_t sepvad_criterion_backward(int32_t B, const float* est, int64_t est_ld, c
                                   const float* vad, const float* labels, const int64_t* perm, int32_t T,
                                   const float* g_vad, float* grad_vad, void* stream);
 
+/* ---- backward of the back end and the VAD head (model/model.py:421-461) -----------------------------
+ * loss.backward() through the forward's tail: torch.istft (model/model.py:438-441), the mask product
+ * est = X sigmoid(masks) (:429-437; the noisy-phase form has the same gradient), the sigmoid, and the VAD head
+ * (:153-179, called at :424-427) on the pre-sigmoid masks. The result is the gradient at masks_b [B][514][T], the trunk's
+ * output, and the gradients of the VAD head's folded parameters (csrc/tail_grad.hip). There is no gradient
+ * with respect to x or est, none through the inference-only branch (:444-457), and final_vad_masked_speakers is refused. */
+enum { SEPVAD_TAIL_NPAR = 5166 };  /* vadw and gpar: conv1_1 weight [4][257][5] (folded: v g / |v|) | output_layer_vad weight
+                                      [4][3] (folded) | its bias | BN_1 weight [4] | BN_1 bias [4] | relu_1 weight | conv1_1
+                                      bias [4] */
+
+/* Device bytes of scratch (256-byte aligned) that sepvad_tail_forward and sepvad_tail_backward need for B utterances of
+ * N samples; negative status for B < 1, B > 32767, N <= 256 or N >= 2^29. */
+int64_t sepvad_tail_scratch_bytes(int32_t B, int32_t N);
+
+/* model/model.py:421-441 on given masks, through launches the forward has: the front end (X = STFT of x, rows of stride
+ * ldx), the multi-kernel schedule's VAD conv1_1 and the forward's back end. masks_fm: pre-sigmoid masks frame-major
+ * [B][Tp][576], Tp = T rounded up to 64, speaker q's bins at [257 q, 257 q + 257), the rest zero. sep [B][2][N]; vad
+ * [B][2][T], ignored without final_vad. Nothing of a handle's forward is touched: every intermediate lives in scratch.
+ * SEPVAD_E_ARG (nothing launched) for a null pointer, a bad shape, final_vad_masked_speakers, a short or misaligned
+ * scratch. */
+int32_t sepvad_tail_forward(sepvad_handle h, const float* x, int64_t ldx, const float* masks_fm, int32_t B, int32_t N,
+                            void* scratch, int64_t scratch_bytes, float* sep, float* vad, void* stream);
+
+/* The backward of model/model.py:421-441 at masks_b [B][2][257][T] (pre-sigmoid, bin-major, as the side attribute) for
+ * the mixtures x the forward ran on. g_sep: upstream gradient of sep [B][2][N] with element strides gs_b, gs_s, gs_n
+ * (>= 0: an expanded scalar has stride 0), NULL for zero; g_vad likewise for vad [B][2][T]. vadw [SEPVAD_TAIL_NPAR] device
+ * doubles: the VAD head's parameters with the two weight-norm folds applied in double (needed with g_vad: the head's
+ * backward runs in double, so the parameter gradients carry one float32 rounding, the caller's). g_masks [B][2][257][T]
+ * (NULL: not wanted) receives d loss / d masks_b, every element written once; gpar [SEPVAD_TAIL_NPAR] doubles (NULL: not
+ * wanted; written only with g_vad) the gradients of the VAD head's folded parameters added over the batch in a fixed order.
+ * X is recomputed from x and the VAD head's forward from the masks (in double), so the call needs nothing a forward left
+ * behind. No atomics: bitwise reproducible, independent of the gradients' strides, and utterance b's masks gradient
+ * depends on its own rows only. SEPVAD_E_ARG (nothing launched) for a null x or masks_b, a bad shape, both gradients
+ * NULL, nothing to compute, g_vad without a VAD head or without vadw, a negative stride, a short or misaligned scratch. */
+int32_t sepvad_tail_backward(sepvad_handle h, const float* x, int64_t ldx, const float* masks_b, int32_t B, int32_t N,
+                             const float* g_sep, int64_t gs_b, int64_t gs_s, int64_t gs_n, const float* g_vad,
+                             int64_t gv_b, int64_t gv_s, int64_t gv_t, const double* vadw, void* scratch,
+                             int64_t scratch_bytes, float* g_masks, double* gpar, void* stream);
+
 /* ---- streaming evaluation with known targets (model/online_class_known_targets.py:85-154) --------
  * The window loop of calc_online (:101-123) for the windows of one sepvad_forward_windows chunk in a fixed number of
  * launches (csrc/stream_eval.hip): each window's PIT against its target window

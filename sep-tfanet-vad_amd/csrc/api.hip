@@ -658,6 +658,106 @@ int32_t sepvad_criterion_backward(int32_t B, const float* est, int64_t est_ld, c
   HIPRET(launch_crit_grad(a, (hipStream_t)stream));
 }
 
+// The tail with a backward (model/model.py:421-461; csrc/tail_grad.hip). Scratch: the forward's
+// frame-major buffers (X | dB spectrum | TCN input | TCN.LN records | conv1_1 output | BN_1 records), overlaid by the
+// backward's (conv1_1 output in double | g_z | g_y in double and in float32 | the rows' partials), every array on a 256-byte boundary.
+namespace {
+static_assert(TG_NPAR == SEPVAD_TAIL_NPAR, "gpar layout (include/sepvad.h)");
+struct TailLayout { int64_t X, specdb, S0, rec_gate, vy, rec_vad, feat, gz, gyd, gy, part_small, part_w1, total; int T, Tp; };
+const char* tail_layout(int32_t B, int32_t N, TailLayout& L) {
+  if (B < 1 || B > 32767) return "need 1 <= B <= 32767";
+  if (N <= HOP || N >= (1 << 29)) return "need 256 < N < 2^29 (reflect padding of the STFT)";
+  L.T = 1 + N / HOP; L.Tp = round_up(L.T, TILE);
+  int64_t at = 0;
+  auto take = [&](int64_t bytes) { const int64_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+  const int64_t rows = (int64_t)B * L.Tp;
+  L.X = take(rows * NBIN * 8); L.specdb = take(rows * SPEC_LD * 4); L.S0 = take(rows * CH * 4);
+  L.rec_gate = take(rows / GATE_ROWS * 2 * 8); L.vy = take(rows * 8 * 4); L.rec_vad = take(rows / VAD_ROWS * 4 * 8);
+  const int64_t fwd = at, bst = (int64_t)B * 2 * L.T;
+  at = 0;
+  L.feat = take(bst * 4 * 8); L.gz = take(bst * 8); L.gyd = take(bst * 4 * 8); L.gy = take(bst * 4 * 4);
+  L.part_small = take((int64_t)B * 2 * TG_NSMALL * 8); L.part_w1 = take((int64_t)B * 2 * tg_w1_chunks(L.T) * TG_NW1 * 8);
+  L.total = std::max(fwd, at);
+  return nullptr;
+}
+int32_t tail_check(const std::string& e, sepvad_handle h, int32_t B, int32_t N, int64_t ldx, const void* scratch,
+                   int64_t scratch_bytes, TailLayout& L) {
+  if (!h) return fail(SEPVAD_E_ARG, e + "null handle");
+  if (const char* why = tail_layout(B, N, L)) return fail(SEPVAD_E_ARG, e + why);
+  if (ldx < N || ldx > INT32_MAX) return fail(SEPVAD_E_ARG, e + "row stride must be >= N");
+  if (h->cfg.final_vad && h->cfg.final_vad_masked_speakers)
+    return fail(SEPVAD_E_ARG, e + "final_vad_masked_speakers has no backward");
+  if (!scratch || scratch_bytes < L.total) return fail(SEPVAD_E_ARG, e + "scratch too small (sepvad_tail_scratch_bytes)");
+  if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail(SEPVAD_E_ARG, e + "scratch must be 256-byte aligned");
+  return SEPVAD_OK;
+}
+}  // namespace
+
+int64_t sepvad_tail_scratch_bytes(int32_t B, int32_t N) {
+  TailLayout L{};
+  if (const char* why = tail_layout(B, N, L)) return fail(SEPVAD_E_ARG, std::string("sepvad_tail_scratch_bytes: ") + why);
+  return L.total;
+}
+
+int32_t sepvad_tail_forward(sepvad_handle h, const float* x, int64_t ldx, const float* masks_fm, int32_t B, int32_t N,
+                            void* scratch, int64_t scratch_bytes, float* sep, float* vad, void* stream) {
+  TailLayout L{};
+  if (const int32_t rc = tail_check("sepvad_tail_forward: ", h, B, N, ldx, scratch, scratch_bytes, L)) return rc;
+  const bool has_vad = h->cfg.final_vad != 0;
+  if (!x || !masks_fm || !sep || (has_vad && !vad)) return fail(SEPVAD_E_ARG, "sepvad_tail_forward: null pointer");
+  DeviceGuard dg(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  char* sc = (char*)scratch;
+  Workspace w{};
+  w.X = (float2*)(sc + L.X); w.specdb = (float*)(sc + L.specdb); w.S0 = (float*)(sc + L.S0);
+  w.rec_gate = (double*)(sc + L.rec_gate); w.vy = (float*)(sc + L.vy); w.rec_vad = (double*)(sc + L.rec_vad);
+  HIPCHK(launch_stft_gate(stft_gate_args(h, w, x, (int)ldx, B, N), s));  // the front end, for X
+  IstftArgs is = istft_pair_args(h, w.X, masks_fm, B, N);
+  if (has_vad) {  // the multi-kernel schedule's VAD stage and tail (forward.hip vad_stage, back_end)
+    Vad1Args v{};
+    v.B = B; v.T = L.T; v.Tp = L.Tp; v.masks = masks_fm; v.X = w.X;
+    v.w1 = h->P(h->v_w1); v.b1 = h->P(h->v_b1); v.alpha = h->v_a; v.vy = w.vy; v.out_rec = w.rec_vad;
+    HIPCHK(launch_vad1(v, s));
+    is.has_vad = 1; is.thr = 0.5f;
+    is.vy = w.vy; is.w2 = h->P(h->v_w2); is.b2 = h->v_b2;
+    is.vgn = GnSrc{w.rec_vad, L.Tp / VAD_ROWS, 2, 0, h->P(h->v_g), h->P(h->v_b), 1e-8f};
+    is.vad_out = vad;
+  }
+  is.y = sep;
+  HIPRET(launch_istft_pair(is, s));
+}
+
+int32_t sepvad_tail_backward(sepvad_handle h, const float* x, int64_t ldx, const float* masks_b, int32_t B, int32_t N,
+                             const float* g_sep, int64_t gs_b, int64_t gs_s, int64_t gs_n, const float* g_vad,
+                             int64_t gv_b, int64_t gv_s, int64_t gv_t, const double* vadw, void* scratch,
+                             int64_t scratch_bytes, float* g_masks, double* gpar, void* stream) {
+  TailLayout L{};
+  if (const int32_t rc = tail_check("sepvad_tail_backward: ", h, B, N, ldx, scratch, scratch_bytes, L)) return rc;
+  if (!x || !masks_b) return fail(SEPVAD_E_ARG, "sepvad_tail_backward: null pointer");
+  if (!g_sep && !g_vad) return fail(SEPVAD_E_ARG, "sepvad_tail_backward: neither upstream gradient");
+  if (!g_masks && !(g_vad && gpar)) return fail(SEPVAD_E_ARG, "sepvad_tail_backward: nothing to compute");
+  if (g_vad && !h->cfg.final_vad) return fail(SEPVAD_E_ARG, "sepvad_tail_backward: g_vad without a VAD head");
+  if (g_vad && !vadw) return fail(SEPVAD_E_ARG, "sepvad_tail_backward: g_vad without the VAD head's parameters");
+  if (gs_b < 0 || gs_s < 0 || gs_n < 0 || gv_b < 0 || gv_s < 0 || gv_t < 0)
+    return fail(SEPVAD_E_ARG, "sepvad_tail_backward: negative stride");
+  DeviceGuard dg(h->device);
+  char* sc = (char*)scratch;
+  TailGradArgs a{};
+  a.B = B; a.N = N; a.T = L.T; a.x = x; a.ldx = ldx; a.masks = masks_b;
+  a.g_sep = g_sep; a.gs_b = gs_b; a.gs_s = gs_s; a.gs_n = gs_n;
+  a.g_vad = g_vad; a.gv_b = gv_b; a.gv_s = gv_s; a.gv_t = gv_t;
+  a.win_x = h->P(h->win_out); a.win_inv = h->P(h->win_inv); a.tw = (const float2*)h->P(h->tw);
+  if (g_vad) {
+    a.vw = vadw; a.eps = 1e-8f;
+    a.feat = (double*)(sc + L.feat); a.gz = (double*)(sc + L.gz);
+    a.gyd = (double*)(sc + L.gyd); a.gy = (float*)(sc + L.gy);
+    a.part_small = (double*)(sc + L.part_small); a.part_w1 = (double*)(sc + L.part_w1);
+    a.gpar = gpar;
+  }
+  a.g_masks = g_masks;
+  HIPRET(launch_tail_grad(a, (hipStream_t)stream));
+}
+
 int32_t sepvad_normalize(const float* x, int64_t n, float* y, void* scratch, void* stream) {
   if (!x || !y || !scratch || n < 1) return fail(SEPVAD_E_ARG, "sepvad_normalize: bad arguments");
   static_assert(NORM_MAX_BLOCKS * 2 * sizeof(float) <= SEPVAD_NORM_SCRATCH_BYTES, "scratch size");

@@ -1,4 +1,4 @@
-// Shared pieces of the LDS FFTs (spectral.hip, istft.hip): complex helpers, the W512 twiddle table access,
+// Shared pieces of the LDS FFTs (spectral.hip, stft.hip, istft.hip, tail_grad.hip): complex helpers, the W512 twiddle table access,
 // the radix-4 Stockham stage and the one-wave 256-point transform.
 #pragma once
 #include "device_common.h"
@@ -134,6 +134,34 @@ __device__ __forceinline__ int mul_late(int c, int k) {
   int r;
   asm volatile("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(c), "s"(k));
   return r;
+}
+
+// Forward real 512-point transform of a frame whose samples are in registers (tail_grad.hip; the operations of
+// stft.hip's rfft512_col after its loads, which keeps its own copy so that the forward's code is untouched): x[n1] = this
+// lane's windowed column z[16 n1 + c] of the 256-point complex sequence z[m] = x[2m] + i x[2m+1] (16 lanes per frame,
+// c = lane & 15). Step 1 DFT over n1, twiddle W256^(c k1), XOR-swizzled transpose through `row`, step 2 DFT over n2 ->
+// Z[c + 16 k2], written to `row` in natural order for the split step (the caller syncs the wave before reading it).
+__device__ __forceinline__ void rfft512_regs(float2 (&x)[16], float2* row, const float2* tw, int c) {
+  dft16<false>(x);  // A[k1] at slot d16(k1)
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k1 = 1; k1 < 16; ++k1) {  // W256^(c k1) = W512^(2 c k1)
+    x[d16(k1)] = cmul(x[d16(k1)], twid<true>(tw, mul_late(c, 2 * k1)));
+    if (k1 % 4 == 3) {
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#pragma unroll
+  for (int k1 = 0; k1 < 16; ++k1) row[16 * k1 + xor_late(c, k1)] = x[d16(k1)];
+  wave_lds_sync();
+#pragma unroll
+  for (int n2 = 0; n2 < 16; ++n2) x[n2] = row[16 * c + xor_late(c, n2)];  // row k1 = c of the transpose
+  wave_lds_sync();  // every lane's reads done before the natural-order writes below
+  dft16<false>(x);  // Z[c + 16 k2] at slot d16(k2)
+  float2* rc = row + c;
+#pragma unroll
+  for (int k2 = 0; k2 < 16; ++k2) rc[16 * k2] = x[d16(k2)];
 }
 
 }  // namespace sepvad

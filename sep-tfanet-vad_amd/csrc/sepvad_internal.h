@@ -392,6 +392,34 @@ struct CritGradArgs {
 };
 hipError_t launch_crit_grad(const CritGradArgs& a, hipStream_t s);
 
+// backward of the back end and the VAD head (tail_grad.hip): from the gradients of sep [B][2][N] and vad [B][2][T] to
+// the gradient at the pre-sigmoid masks [B][2][257][T] and the VAD head's parameter gradients
+constexpr int TG_OWN = 16;        // frames per workgroup of k_tail_grad_masks
+constexpr int TG_NW1 = 4 * NBIN * 5;  // folded conv1_1 weights [4][257][5]
+constexpr int TG_NSMALL = 26;     // w2 [4][3] | b2 | BN_1 weight [4] | BN_1 bias [4] | PReLU | conv1_1 bias [4]
+constexpr int TG_NPAR = TG_NW1 + TG_NSMALL;
+constexpr int TG_W1_T = 64;       // frames per partial row of the conv1_1 weight gradient
+__host__ __device__ inline int tg_w1_chunks(int T) { return (T + TG_W1_T - 1) / TG_W1_T; }
+struct TailGradArgs {
+  int B, N, T;
+  const float* x; long long ldx;      // [B][ldx] mixtures
+  const float* masks;                 // [B][2][257][T] pre-sigmoid (masks_b)
+  const float* g_sep; long long gs_b, gs_s, gs_n;   // upstream gradient of sep and its element strides; null: zero
+  const float* g_vad; long long gv_b, gv_s, gv_t;   // upstream gradient of vad and its element strides; null: zero
+  const float* win_x; const float* win_inv;         // spec_output.window, inv_spec.window [512]
+  const float2* tw;                   // [512] e^{-2 pi i m / 512}
+  const double* vw;                   // [TG_NPAR] the VAD head's parameters, weights folded, in the layout of gpar
+  float eps;                          // BN_1
+  double* feat;                       // scratch [B*2][4][T] conv1_1 output y (before the PReLU)
+  double* gz;                         // scratch [B*2][T] gradient before the output sigmoid
+  double* gyd; float* gy;             // scratch [B*2][4][T] gradient at y, and its float32 rounding (k_tail_grad_masks)
+  double* part_small;                 // scratch [B*2][TG_NSMALL]
+  double* part_w1;                    // scratch [B*2][tg_w1_chunks(T)][TG_NW1]
+  double* gpar;                       // [TG_NPAR] folded parameter gradients (null: no VAD part)
+  float* g_masks;                     // [B][2][257][T] (null: parameter gradients only)
+};
+hipError_t launch_tail_grad(const TailGradArgs& a, hipStream_t s);
+
 // streaming evaluation with known targets (stream_eval.hip): one chunk of n windows (first window k0 of K) of B streams
 constexpr int SE_NV = 12;          // doubles per (window, segment, stream): SE_* in stream_eval.hip
 constexpr int SE_MAX_SEG = 4096;   // hop segments of one window's overlap, ceil((W - H) / H), kept in LDS by the chain

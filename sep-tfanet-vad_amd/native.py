@@ -118,6 +118,9 @@ _ABI = {
     "sepvad_eval_vad": (i32, (P, P, i32, P, P, i32, i32, P, P, P, P, P, P, P)),
     "sepvad_criterion_coef": (i32, (P, i64, P, i64, i32, i64, i32, i32, i32, dbl, P, i64, P, P, P)),
     "sepvad_criterion_backward": (i32, (i32, P, i64, P, i64, i64, P, P, P, i64, P, P, P, i32, P, P, P)),
+    "sepvad_tail_scratch_bytes": (i64, (i32, i32)),
+    "sepvad_tail_forward": (i32, (P, P, i64, P, i32, i32, P, i64, P, P, P)),
+    "sepvad_tail_backward": (i32, (P, P, i64, P, i32, i32, P, i64, i64, i64, P, i64, i64, i64, P, P, i64, P, P, P)),
     "sepvad_stream_eval_scratch_bytes": (i64, (i32, i32, i64, i64, i32)),
     "sepvad_stream_eval": (i32, (P, i64, i32, i32, i32, i32, i64, i64, P, i64, i32, i32, i32, i32, dbl, P, i64, P, i64,
                                  P, P, P, P, P, P, i64, P)),

@@ -1,0 +1,344 @@
+"""The backward of the forward's tail on the device (train_tail.TrainableTail; csrc/tail_grad.hip: sepvad_tail_forward,
+sepvad_tail_backward) against
+
+* the reference's own float64 autograd (tests/golden/golden_tail_grad.npz) with the yardstick the golden maker stored;
+* float64 autograd of tail_grad_cases' restatement (pinned to the reference by test_tail_grad_host.py) for the shapes too
+  large to commit, with the yardstick computed here on the CPU: the restatement in float32 autograd;
+* itself: the forward's bits, reproducibility, independence of the batch, of the upstream gradients' strides and of
+  whatever ran on the stream in between.
+
+Gate (tail_grad_cases): the native error stays within 2 times the yardstick's error of the same case. Masks gradient:
+per (b, speaker, frame), in units of 2^-24 of that frame's largest float64 gradient. Parameter gradients: in units of
+2^-24 of each tensor's maximum.
+
+Shapes. N = 257 (T = 2) stands where a T = 1 case would: the reference and the forward both refuse N <= 256 (reflect
+padding of the STFT), so the shortest utterance has two frames, each with conv taps in the padding. N = 3840 and 4096
+put T at one k_tail_grad_masks workgroup's 16 frames and at one more. 8191 and 8193: N % 256 = 255 and 1, the overlap-add
+envelope near zero at the last sample, even and odd T.
+
+Saturated masks. sigmoid(30) is exactly 1 in float32, so m (1 - m) and the separation gradient are exactly zero at +30. At
+-30 m = 9.4e-14 is a normal float32 and m (1 - m) is not zero, in torch's own sigmoid backward either: there the gradient
+must be finite and below 2^-43 of the unsaturated gradient's maximum (m (1 - m) < 2^-43).
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import tail_grad_cases as tc
+from conftest import GOLDEN, config_of
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+SCHED_TOL, VAD_SCHED_TOL = 1e-5, 1e-4   # test_gpu_fused.py: the two schedules' sep and vad
+GOLDEN_TAGS = ("n257", "n700", "n2816")
+OWN = 16                                 # TG_OWN (csrc/sepvad_internal.h)
+SHAPES = [(B, N) for N in (257, 700, 256 * (OWN - 1), 256 * OWN, 8191, 8193, 8292) for B in (1, 3)] + [(2, 32000)]
+
+
+def t_(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+@pytest.fixture(scope="module")
+def g():
+    return np.load(f"{GOLDEN}/golden_tail_grad.npz")
+
+
+def build(cname, state_dicts):
+    import sep_tfanet_vad_amd as pkg
+    net = pkg.SeparationModel(**config_of(cname))
+    net.load_state_dict(state_dicts[cname], strict=True)
+    return net.eval().to(DEV)
+
+
+@pytest.fixture(scope="module")
+def net(state_dicts):
+    return build("with_vad", state_dicts)
+
+
+@pytest.fixture()
+def tail(net):
+    from sep_tfanet_vad_amd import train_tail
+    net.zero_grad()
+    return train_tail.TrainableTail(net)
+
+
+def vad_params(sd):
+    return {k: sd[k] for k in tc.VAD_PARAMS}
+
+
+def native_grads(tail, x, masks, g_sep, g_vad):
+    """from_masks on a fresh leaf and one backward of <sep, g_sep> + <vad, g_vad> (a None term left out) ->
+    dict(masks=..., <parameter name>=... | None, sep, vad), on the CPU."""
+    tail.net.zero_grad()
+    m = masks.to(DEV).requires_grad_(True)
+    sep, vad = tail.from_masks(x.to(DEV), m)
+    loss = 0
+    if g_sep is not None:
+        loss = loss + (sep * g_sep.to(DEV)).sum()
+    if g_vad is not None:
+        loss = loss + (vad * g_vad.to(DEV)).sum()
+    loss.backward()
+    named = dict(tail.net.named_parameters())
+    out = dict(masks=m.grad.cpu(), sep=sep.detach().cpu(), vad=vad.detach().cpu())
+    for k in tc.VAD_PARAMS:
+        out[k] = named[k].grad.cpu() if named[k].grad is not None else None
+    return out
+
+
+def gate(r, truth, yard, mode, where):
+    """Print every figure, then assert the gate."""
+    assert r["masks"].dtype == torch.float32 and bool(torch.isfinite(r["masks"]).all())
+    rows = [("masks", tc.frame_units(r["masks"], truth["masks"]), yard["masks"])]
+    if mode != "sep":
+        rows += [(k, tc.tensor_units(r[k], truth[k]), yard[k]) for k in tc.VAD_PARAMS]
+    else:
+        assert all(r[k] is None for k in tc.VAD_PARAMS)
+    for name, units, y in rows:
+        print(f"{where} {mode} {name}: native {units:.2f}, yardstick {y:.2f} (2^-24 units)")
+    for name, units, y in rows:
+        assert units <= tc.MARGIN * y, (where, mode, name, units, y)
+
+
+# ---- 1. the reference's goldens ----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("mode", tc.MODES)
+@pytest.mark.parametrize("tag", GOLDEN_TAGS)
+def test_golden_case(g, tail, tag, mode):
+    x, masks = t_(g[f"{tag}_x"]), t_(g[f"{tag}_masks"])
+    gs, gv = tc.split_modes(t_(g[f"{tag}_g_sep"]), t_(g[f"{tag}_g_vad"]), mode)
+    r = native_grads(tail, x, masks, gs, gv)
+    truth = dict(masks=t_(g[f"{tag}_{mode}_masks_f64"]), **{k: t_(g[f"{tag}_{k}_f64"]) for k in tc.VAD_PARAMS})
+    yard = dict(masks=float(g[f"{tag}_{mode}_yard_masks"]))
+    if mode != "sep":
+        yard.update({k: float(g[f"{tag}_{mode}_yard_{k}"]) for k in tc.VAD_PARAMS})
+    gate(r, truth, yard, mode, tag)
+    assert float((r["sep"].double() - t_(g[f"{tag}_sep_f64"])).abs().max()) <= 1e-4   # SEP_TOL of the parity tests
+    assert float((r["vad"].double() - t_(g[f"{tag}_vad_f64"])).abs().max()) <= 1e-3   # VAD_PROB_TOL
+
+
+# ---- 2. the shapes, against the restatement ------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def cpu_case(B, N):
+    """Inputs, the float64 truth and the float32 yardstick of every mode, computed once per shape."""
+    from sep_tfanet_vad_amd import synth
+    sd = {k: t_(v) for k, v in synth.make_state_dict(config_of("with_vad"), 1234).items()}
+    x, masks, g_sep, g_vad = tc.seeded_case(B, N, seed=7000 + N + B)
+    truth, yard = {}, {}
+    for mode in tc.MODES:
+        gs, gv = tc.split_modes(g_sep, g_vad, mode)
+        args = (x, masks, vad_params(sd), sd["inv_spec.window"], gs, gv)
+        truth[mode] = tc.autograd_grads(*args, torch.float64)
+        r32 = tc.autograd_grads(*args, torch.float32)
+        yard[mode] = {k: (tc.frame_units if k == "masks" else tc.tensor_units)(r32[k], truth[mode][k]) for k in r32}
+    return x, masks, g_sep, g_vad, truth, yard
+
+
+@pytest.mark.parametrize("mode", tc.MODES)
+@pytest.mark.parametrize("B,N", SHAPES)
+def test_shapes(tail, B, N, mode):
+    x, masks, g_sep, g_vad, truth, yard = cpu_case(B, N)
+    gs, gv = tc.split_modes(g_sep, g_vad, mode)
+    gate(native_grads(tail, x, masks, gs, gv), truth[mode], yard[mode], mode, f"B={B} N={N}")
+
+
+# ---- 3. the forward ------------------------------------------------------------------------------------------------
+
+def test_tail_returns_the_forwards_bits(net, tail):
+    x = tc.seeded_case(3, 8292, seed=11)[0].to(DEV)
+    with torch.no_grad():
+        sep0, vad0, _ = net(x)
+        mb0 = net.masks_b.clone()
+    sep, vad, masks_b = tail(x)
+    assert torch.equal(sep, sep0) and torch.equal(vad, vad0) and torch.equal(masks_b, mb0)
+    assert masks_b.is_leaf and masks_b.requires_grad and sep.requires_grad and vad.requires_grad
+    sep2, vad2 = tail.from_masks(x, mb0)
+    assert float((sep2.detach() - sep0).abs().max()) <= SCHED_TOL
+    assert float((vad2.detach() - vad0).abs().max()) <= VAD_SCHED_TOL
+    # the node built around the forward's tensors gives the gradients of the node that computed them
+    g_sep, g_vad = torch.randn_like(sep0), torch.randn_like(vad0)
+    ((sep * g_sep).sum() + (vad * g_vad).sum()).backward()
+    m = mb0.clone().requires_grad_(True)
+    net.zero_grad()
+    s3, v3 = tail.from_masks(x, m)
+    ((s3 * g_sep).sum() + (v3 * g_vad).sum()).backward()
+    assert torch.equal(masks_b.grad, m.grad)
+
+
+def test_without_final_vad():
+    import sep_tfanet_vad_amd as pkg
+    from sep_tfanet_vad_amd import synth, train_tail
+    cfg = dict(config_of("with_vad"), final_vad=False)
+    sd = {k: t_(v) for k, v in synth.make_state_dict(cfg, 1234).items()}
+    net = pkg.SeparationModel(**cfg)
+    net.load_state_dict(sd, strict=True)
+    net = net.eval().to(DEV)
+    tail = train_tail.TrainableTail(net)
+    x, _, g_sep, _ = tc.seeded_case(2, 4096, seed=12)
+    with torch.no_grad():
+        sep0, vad0, _ = net(x.to(DEV))
+    sep, vad, masks_b = tail(x.to(DEV))
+    assert isinstance(vad0, int) and vad0 == 0 and isinstance(vad, int) and vad == 0 and torch.equal(sep, sep0)
+    (sep * g_sep.to(DEV)).sum().backward()
+    m = masks_b.detach().clone().requires_grad_(True)
+    s2, v2 = tail.from_masks(x.to(DEV), m)
+    assert isinstance(v2, int) and v2 == 0
+    (s2 * g_sep.to(DEV)).sum().backward()
+    assert torch.equal(m.grad, masks_b.grad)
+    args = (x, masks_b.detach().cpu(), None, sd["inv_spec.window"], g_sep, None)
+    truth = tc.autograd_grads(*args, torch.float64)
+    r32 = tc.autograd_grads(*args, torch.float32)
+    units, yard = tc.frame_units(m.grad.cpu(), truth["masks"]), tc.frame_units(r32["masks"], truth["masks"])
+    print("final_vad=False masks: native", units, "yardstick", yard)
+    assert units <= tc.MARGIN * yard
+
+
+# ---- 4. edge values ------------------------------------------------------------------------------------------------
+
+def test_saturated_masks(tail):
+    x, masks, g_sep, _ = tc.seeded_case(2, 4096, seed=13)
+    ref = native_grads(tail, x, torch.zeros_like(masks), g_sep, None)["masks"]   # m (1 - m) = 1/4 exactly
+    hi = native_grads(tail, x, torch.full_like(masks, 30.0), g_sep, None)["masks"]
+    lo = native_grads(tail, x, torch.full_like(masks, -30.0), g_sep, None)["masks"]
+    assert bool(torch.isfinite(hi).all()) and not bool(hi.any())
+    assert bool(torch.isfinite(lo).all()) and float(lo.abs().max()) <= 2.0 ** -43 * 4 * float(ref.abs().max())
+
+
+def test_silent_utterance_in_a_batch(tail):
+    x, masks, g_sep, g_vad = tc.seeded_case(3, 4100, seed=14)
+    x[1] = 0.0
+    r = native_grads(tail, x, masks, g_sep, g_vad)
+    assert all(bool(torch.isfinite(v).all()) for v in r.values())
+    sep_only = native_grads(tail, x, masks, g_sep, None)["masks"]
+    assert not bool(sep_only[1].any()) and bool(sep_only[0].any()) and bool(sep_only[2].any())
+    assert not bool(r["sep"][1].any())
+
+
+# ---- 5. how a trainer binds ------------------------------------------------------------------------------------------
+
+def test_gradients_reach_learned_criterion_weights(tail):
+    from sep_tfanet_vad_amd import combined_loss, pit, sdr, train_criterion
+    crit = train_criterion.CombinedLoss(
+        pit.PITLossWrapper(sdr.PairwiseNegSDR("sisdr", zero_mean=True, take_log=True), pit_from="pw_mtx"),
+        pit.PITLossWrapper(combined_loss.BinaryCrossEntropyLoss_Mean(), pit_from="pw_pt"),
+        dict(weight_separation_loss=0.99, weight_vad_loss=0.01, learn_weight_bool=True)).to(DEV)
+    x, _, tgt, _ = tc.seeded_case(2, 8000, seed=15)
+    labels = (torch.rand(2, 2, 32) > 0.5).float().to(DEV)
+    sep, vad, masks_b = tail(x.to(DEV))
+    sep_loss, vad_loss, _, _ = crit(sep, tgt.to(DEV), vad, labels)
+    (0.99 * sep_loss + 0.01 * vad_loss).backward()
+    named = dict(tail.net.named_parameters())
+    for t in [masks_b, crit.learn_weight_vadLoss, crit.learn_weight_separationLoss] + [named[k] for k in tc.VAD_PARAMS]:
+        assert t.grad is not None and bool(torch.isfinite(t.grad).all()) and bool(t.grad.any())
+    assert all(p.grad is None for k, p in named.items() if k not in tc.VAD_PARAMS)
+
+
+def test_a_chained_torch_head_receives_its_gradients(tail):
+    x, masks, g_sep, g_vad = tc.seeded_case(2, 2816, seed=16)
+    head = torch.nn.Conv1d(514, 514, 1).to(DEV)
+    feats = masks.to(DEV)
+    sep, vad = tail.from_masks(x.to(DEV), head(feats))
+    ((sep * g_sep.to(DEV)).sum() + (vad * g_vad.to(DEV)).sum()).backward()
+    m = head(feats).detach().requires_grad_(True)
+    tail.net.zero_grad()
+    s2, v2 = tail.from_masks(x.to(DEV), m)
+    ((s2 * g_sep.to(DEV)).sum() + (v2 * g_vad.to(DEV)).sum()).backward()
+    want_w = torch.einsum("bot,bit->oi", m.grad, feats).unsqueeze(-1)
+    assert float((head.weight.grad - want_w).abs().max()) <= 1e-4 * float(want_w.abs().max())
+    assert float((head.bias.grad - m.grad.sum((0, 2))).abs().max()) <= 1e-4 * float(m.grad.sum((0, 2)).abs().max())
+
+
+def test_refusals(net, tail, state_dicts):
+    import sep_tfanet_vad_amd as pkg
+    from sep_tfanet_vad_amd import train_tail
+    x, masks, _, _ = tc.seeded_case(1, 2816, seed=17)
+    with pytest.raises(ValueError, match="inference_kw"):
+        tail(x.to(DEV), dict(pkg.INFERENCE_KW_DEFAULTS))
+    masked = pkg.SeparationModel(**dict(config_of("with_vad"), final_vad_masked_speakers=True))
+    with pytest.raises(NotImplementedError, match="final_vad_masked_speakers"):
+        train_tail.TrainableTail(masked)
+    with pytest.raises(RuntimeError, match="gradient with respect to x"):
+        tail(x.to(DEV).requires_grad_(True))
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        tail(x)
+    with pytest.raises(ValueError, match="masks_b"):
+        tail.from_masks(x.to(DEV), masks.to(DEV)[:, :, :-1])
+    m = masks.to(DEV).requires_grad_(True)
+    sep, vad = tail.from_masks(x.to(DEV), m)
+    up = torch.ones_like(sep).requires_grad_(True)   # a double backward would differentiate the backward by this
+    (gm,) = torch.autograd.grad([sep, vad], m, grad_outputs=[up, torch.ones_like(vad)], create_graph=True)
+    with pytest.raises(RuntimeError, match="once_differentiable"):
+        gm.sum().backward()
+
+
+# ---- 6. bits ---------------------------------------------------------------------------------------------------------
+
+def run_bits(tail, x, masks, grads):
+    """-> (masks gradient, the nine parameter gradients) on the device for the upstream gradients `grads` as given."""
+    tail.net.zero_grad()
+    m = masks.to(DEV).requires_grad_(True)
+    sep, vad = tail.from_masks(x.to(DEV), m)
+    torch.autograd.backward([sep, vad], list(grads))
+    named = dict(tail.net.named_parameters())
+    return m.grad, [named[k].grad.clone() for k in tc.VAD_PARAMS]
+
+
+def test_two_backwards_give_the_same_bits(tail):
+    x, masks, g_sep, g_vad = tc.seeded_case(3, 8292, seed=18)
+    a = run_bits(tail, x, masks, (g_sep.to(DEV), g_vad.to(DEV)))
+    b = run_bits(tail, x, masks, (g_sep.to(DEV), g_vad.to(DEV)))
+    assert torch.equal(a[0], b[0]) and all(torch.equal(p, q) for p, q in zip(a[1], b[1]))
+
+
+def test_an_utterances_masks_gradient_does_not_depend_on_its_batch(tail):
+    x, masks, g_sep, g_vad = tc.seeded_case(3, 8292, seed=19)
+    whole = run_bits(tail, x, masks, (g_sep.to(DEV), g_vad.to(DEV)))[0]
+    for b in range(3):
+        alone = run_bits(tail, x[b:b + 1], masks[b:b + 1], (g_sep[b:b + 1].to(DEV), g_vad[b:b + 1].to(DEV)))[0]
+        assert torch.equal(alone[0], whole[b]), b
+
+
+def test_upstream_gradient_strides(tail):
+    x, masks, g_sep, g_vad = tc.seeded_case(2, 8193, seed=20)
+    gs, gv = g_sep.to(DEV), g_vad.to(DEV)
+    clean = run_bits(tail, x, masks, (gs, gv))
+    wide_s, wide_v = torch.zeros(2, 2, 8193, 2, device=DEV), torch.zeros(2, 3, 33, 2, device=DEV)
+    wide_s[..., 1], wide_v[:, :2, :, 0] = gs, gv
+    views = (wide_s[..., 1], wide_v[:, :2, :, 0])
+    assert not views[0].is_contiguous() and not views[1].is_contiguous()
+    strided = run_bits(tail, x, masks, views)
+    assert torch.equal(clean[0], strided[0]) and all(torch.equal(p, q) for p, q in zip(clean[1], strided[1]))
+    # sep.sum() + vad.sum(): stride-0 expansions of a scalar
+    ones = run_bits(tail, x, masks, (torch.ones_like(gs), torch.ones_like(gv)))
+    tail.net.zero_grad()
+    m = masks.to(DEV).requires_grad_(True)
+    sep, vad = tail.from_masks(x.to(DEV), m)
+    (sep.sum() + vad.sum()).backward()
+    named = dict(tail.net.named_parameters())
+    assert torch.equal(m.grad, ones[0]) and all(torch.equal(named[k].grad, q) for k, q in zip(tc.VAD_PARAMS, ones[1]))
+    # an unused output: its gradient is None, which means zero
+    tail.net.zero_grad()
+    m2 = masks.to(DEV).requires_grad_(True)
+    sep, vad = tail.from_masks(x.to(DEV), m2)
+    (sep * gs).sum().backward()
+    zero_v = run_bits(tail, x, masks, (gs, torch.zeros_like(gv)))[0]
+    assert float((m2.grad - zero_v).abs().max()) == 0.0
+
+
+def test_backward_after_an_unrelated_forward(net, tail):
+    x, masks, g_sep, g_vad = tc.seeded_case(2, 8292, seed=21)
+    gs, gv = g_sep.to(DEV), g_vad.to(DEV)
+    sep, vad, masks_b = tail(x.to(DEV))
+    clean_m = run_bits(tail, x, masks_b.detach(), (gs, gv))
+    net.zero_grad()
+    other = tc.seeded_case(3, 12345, seed=22)
+    with torch.no_grad():
+        net(other[0].to(DEV))                      # replaces the stream's workspace
+        tail.from_masks(other[0].to(DEV), other[1].to(DEV))   # and the shared scratch
+    torch.autograd.backward([sep, vad], [gs, gv])
+    named = dict(net.named_parameters())
+    assert torch.equal(masks_b.grad, clean_m[0])
+    assert all(torch.equal(named[k].grad, q) for k, q in zip(tc.VAD_PARAMS, clean_m[1]))
