@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SEPVAD_ABI_VERSION 1
+#define SEPVAD_ABI_VERSION 2
 
 enum {
   SEPVAD_OK = 0,
@@ -212,14 +212,6 @@ int32_t sepvad_istft_pair_test(sepvad_handle h, const void* X_fm, const float* m
  * [B][roundup(T, 64)][256] channel-last. NULL disables. F16X3 arithmetic only (a separate instantiation of the
  * kernel); tests only (the reference golden's tcn_in, blk0_res, blk0_att). */
 int32_t sepvad_set_tcn_dump(sepvad_handle h, float* dump);
-
-/* Front-end / back-end stages alone, for kernel-level parity tests:
- * STFT with DC zeroed (model/model.py:16-25,408-410) -> X [B, n_fft/2+1, T] complex64, and
- * 10 log10(clamp(|X|^2, 1e-10)) (model/model.py:411-412) -> spec [B, n_fft/2+1, T] (nullable). */
-int32_t sepvad_stft(sepvad_handle h, const float* x, int32_t B, int32_t N, void* X, float* spec,
-                    void* stream);
-/* torch.istft(center=True, length=N) of est [B*S, n_fft/2+1, T] complex64 (model/model.py:460). */
-int32_t sepvad_istft(sepvad_handle h, const void* est, int32_t BS, int32_t N, float* y, void* stream);
 
 /* ---- streaming wrapper (model/online_class_unknown_targets.py:72-105) -------------------------
  * Signals are [B, 2, ld] f32 device arrays (speaker rows of stride ld).

@@ -294,32 +294,6 @@ int32_t sepvad_istft_pair_test(sepvad_handle h, const void* X_fm, const float* m
   HIPRET(launch_istft_pair(is, (hipStream_t)stream));
 }
 
-int32_t sepvad_stft(sepvad_handle h, const float* x, int32_t B, int32_t N, void* X, float* spec, void* stream) {
-  if (!h || !x || B < 1 || N <= HOP) return fail(SEPVAD_E_ARG, "sepvad_stft: bad arguments");
-  DeviceGuard dg(h->device);
-  const int T = 1 + N / HOP;
-  StftArgs sa{};
-  sa.B = B; sa.N = N; sa.ldx = N; sa.T = T; sa.Tp = round_up(T, TILE); sa.x = x; sa.nstr = B; sa.hopw = 0;
-  sa.window = h->P(h->win_out); sa.tw = (const float2*)h->P(h->tw);
-  sa.Xout = (float2*)X; sa.spec_out = h->same_stft_window ? spec : nullptr;
-  HIPCHK(launch_stft(sa, (hipStream_t)stream));
-  if (!h->same_stft_window && spec) {
-    sa.window = h->P(h->win_in); sa.Xout = nullptr; sa.spec_out = spec;
-    HIPCHK(launch_stft(sa, (hipStream_t)stream));
-  }
-  return SEPVAD_OK;
-}
-
-int32_t sepvad_istft(sepvad_handle h, const void* est, int32_t BS, int32_t N, float* y, void* stream) {
-  if (!h || !est || !y || BS < 1 || N <= HOP) return fail(SEPVAD_E_ARG, "sepvad_istft: bad arguments");
-  DeviceGuard dg(h->device);
-  const int T = 1 + N / HOP;
-  IstftArgs is{};
-  is.BS = BS; is.S = 1; is.N = N; is.T = T; is.Tp = round_up(T, TILE); is.est_mode = 0;
-  is.est_in = (const float2*)est; is.window = h->P(h->win_inv); is.tw = (const float2*)h->P(h->tw); is.y = y;
-  HIPRET(launch_istft(is, (hipStream_t)stream));
-}
-
 int32_t sepvad_pit_l1(const float* est, int64_t est_ld, const float* ref, int64_t ref_ld, int32_t B, int64_t L,
                       void* scratch, int64_t* perm_out, float* loss_out, float* pw_out, void* stream) {
   if (!est || !ref || !scratch || B < 1 || L < 1 || est_ld < L || ref_ld < L)

@@ -1,5 +1,5 @@
-// Shared pieces of the LDS FFTs (spectral.hip, stft.hip, istft.hip, tail_grad.hip): complex helpers, the W512 twiddle table access,
-// the radix-4 Stockham stage and the one-wave 256-point transform.
+// Shared pieces of the register-resident FFTs (stft.hip, istft.hip, tail_grad.hip): complex helpers, the W512 twiddle
+// table access and the 16-point DFTs of the four-step 256 = 16 x 16 transform.
 #pragma once
 #include "device_common.h"
 
@@ -14,61 +14,14 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
 }
 __device__ __forceinline__ float2 conjf2(float2 a) { return make_float2(a.x, -a.y); }
 
-// One radix-4 Stockham stage (stride Ns) of a 256-point transform, one wave (lane = j).
-// Twiddle W512^idx, idx in [0, 512). HALF: the table holds only W512^0..255 (W512^(x+256) = -W512^x).
-template <bool HALF>
+// Twiddle W512^idx, idx in [0, 512), from the half table tw = W512^0..255 (W512^(x+256) = -W512^x).
 __device__ __forceinline__ float2 twid(const float2* tw, int idx) {
-  if constexpr (HALF) {
-    const float2 w = tw[idx & 255];
-    return idx < 256 ? w : make_float2(-w.x, -w.y);
-  } else {
-    return tw[idx];
-  }
-}
-
-template <bool INV, bool HALF = false>
-__device__ __forceinline__ void fft_stage(const float2* in, float2* out, const float2* tw, int lane, int Ns) {
-  const int j = lane;
-  const int k = j & (Ns - 1);
-  float2 v[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) v[r] = in[j + r * 64];
-  if (Ns > 1) {
-#pragma unroll
-    for (int r = 1; r < 4; ++r) {
-      float2 w = twid<HALF>(tw, 2 * ((r * k * (64 / Ns)) & 255));  // W_256^(r k 64/Ns) = W_512^(2 ...)
-      if (INV) w.y = -w.y;
-      v[r] = cmul(v[r], w);
-    }
-  }
-  const float2 a0 = cadd(v[0], v[2]), a1 = csub(v[0], v[2]);
-  const float2 a2 = cadd(v[1], v[3]);
-  float2 a3 = csub(v[1], v[3]);
-  a3 = INV ? make_float2(-a3.y, a3.x) : make_float2(a3.y, -a3.x);
-  const int idxD = (j / Ns) * Ns * 4 + k;
-  out[idxD] = cadd(a0, a2);
-  out[idxD + Ns] = cadd(a1, a3);
-  out[idxD + 2 * Ns] = csub(a0, a2);
-  out[idxD + 3 * Ns] = csub(a1, a3);
-}
-
-
-// 256-point transform of one wave ping-ponging between its buffers b0 and b1 (4 stages: result back
-// in b0); the caller's buffers must be complete for this wave (wave_lds_sync or a barrier) on entry.
-template <bool INV, bool HALF = false>
-__device__ inline void fft256(float2* b0, float2* b1, const float2* tw, int lane) {
-  fft_stage<INV, HALF>(b0, b1, tw, lane, 1);
-  wave_lds_sync();
-  fft_stage<INV, HALF>(b1, b0, tw, lane, 4);
-  wave_lds_sync();
-  fft_stage<INV, HALF>(b0, b1, tw, lane, 16);
-  wave_lds_sync();
-  fft_stage<INV, HALF>(b1, b0, tw, lane, 64);
-  wave_lds_sync();
+  const float2 w = tw[idx & 255];
+  return idx < 256 ? w : make_float2(-w.x, -w.y);
 }
 
 // ------------------------------------------------------------------------------------------
-// Register-resident 16-point DFTs for the four-step 256 = 16 x 16 transform (fft16x16_*: 16 lanes per
+// Register-resident 16-point DFTs for the four-step 256 = 16 x 16 transform (16 lanes per
 // transform, 4 transforms per wave, one XOR-swizzled LDS transpose in the frame's own row).
 // dft4: X_k = sum_n v_n W4^(nk), W4 = -i (forward) or +i (inverse), in place.
 template <bool INV>
@@ -146,7 +99,7 @@ __device__ __forceinline__ void rfft512_regs(float2 (&x)[16], float2* row, const
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int k1 = 1; k1 < 16; ++k1) {  // W256^(c k1) = W512^(2 c k1)
-    x[d16(k1)] = cmul(x[d16(k1)], twid<true>(tw, mul_late(c, 2 * k1)));
+    x[d16(k1)] = cmul(x[d16(k1)], twid(tw, mul_late(c, 2 * k1)));
     if (k1 % 4 == 3) {
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);

@@ -218,7 +218,7 @@ inline StftArgs stft_gate_args(const sepvad_model* h, const Workspace& w, const 
 // k_istft_pair without a VAD: est = X * sigmoid(masks) -> iSTFT of B utterances x 2 speakers
 inline IstftArgs istft_pair_args(const sepvad_model* h, const float2* X, const float* masks, int B, int N) {
   IstftArgs is{};
-  is.BS = B * 2; is.S = 2; is.N = N; is.T = 1 + N / HOP; is.Tp = round_up(is.T, TILE); is.est_mode = 1;
+  is.BS = B * 2; is.N = N; is.T = 1 + N / HOP; is.Tp = round_up(is.T, TILE);
   is.X = X; is.masks = masks;
   is.window = h->P(h->win_inv); is.tw = (const float2*)h->P(h->tw);
   return is;

@@ -8,7 +8,7 @@
 namespace sepvad {
 
 // Inverse real 512-point transform of one est row (16 lanes per frame, c = lane & 15) as the 256-point
-// complex inverse transform of z[m] = x[2m] + i x[2m+1] (as in k_istft): the split step produces this
+// complex inverse transform of z[m] = x[2m] + i x[2m+1]: the split step produces this
 // lane's column z[16 r + c] directly in registers; step 1 DFT over r; twiddle W256^(-c k1); XOR-swizzled
 // transpose through the row (element (k1, n2) at 16 k1 + (n2 ^ k1): conflict-free both ways); step 2 DFT
 // over n2 gives z[c + 16 k2]; the windowed, scaled time samples overwrite the row. The caller's row must be
@@ -47,7 +47,7 @@ __device__ __forceinline__ void irfft512_col(float2* Y, float gain, const float2
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int k1 = 1; k1 < 16; ++k1) {  // W256^(-c k1) = conj(W512^(2 c k1))
-    float2 w = twid<true>(tw, mul_late(c, 2 * k1));
+    float2 w = twid(tw, mul_late(c, 2 * k1));
     w.y = -w.y;
     x[d16(k1)] = cmul(x[d16(k1)], w);
     if (k1 % 4 == 3) {
@@ -80,10 +80,10 @@ __device__ __forceinline__ void irfft512_col(float2* Y, float gain, const float2
 }
 
 // ------------------------------------------------------------------------------------------
-// The forward's back end (est_mode 1): one workgroup (8 waves) per (utterance, chunk of IP_OWN frames) for
+// The forward's back end: one workgroup (8 waves) per (utterance, chunk of IP_OWN frames) for
 // BOTH speakers, so each X row is read once for the two masks. Frames [f0-1, f0+IP_OWN) of both speakers:
-// 2 * IP_FR = 24 transforms, 3 rounds of 8 waves; owned output segments [f0, f0+IP_OWN) (+ segment T for
-// the last chunk). The transforms run in place in the frames' own LDS rows (fft256_inplace), so the
+// 2 * IP_FR = 24 transforms, four per wave on waves 0..5; owned output segments [f0, f0+IP_OWN) (+ segment T for
+// the last chunk). The transforms run in place in the frames' own LDS rows (irfft512_col), so the
 // workgroup needs ~52 KB: three per CU, and at T = 126 the 64 x 12 workgroups of a B = 64 forward are all
 // resident at once (one round). Overlap-add: one reciprocal window envelope per thread (its sample phase q
 // is fixed across its segments), then products.
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(512, ISTFT_WAVES) void k_istft_pair(IstftArgs a) {
 }
 
 hipError_t launch_istft_pair(const IstftArgs& a, hipStream_t s) {
-  if (a.S != 2 || a.BS % 2 || a.est_mode != 1) return hipErrorInvalidValue;
+  if (a.BS % 2) return hipErrorInvalidValue;
   dim3 grid(a.BS / 2, (a.T + IP_OWN - 1) / IP_OWN);
   hipLaunchKernelGGL(k_istft_pair, grid, dim3(512), 0, s, a);
   return hipGetLastError();

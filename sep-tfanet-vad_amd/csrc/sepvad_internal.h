@@ -141,25 +141,25 @@ struct GateArgs {
 };
 constexpr int GATE_ROWS = 16;
 
-struct StftArgs {
+struct StftArgs {        // k_stft_gate: STFT + dB spectrum + activity gate
   int B, N, ldx, T, Tp;
   int nstr;              // utterance u reads x + (u % nstr) * ldx + (u / nstr) * hopw: nstr = B, hopw = 0 for a
   long long hopw;        // plain batch; streaming windows: u = window * nstr + stream (sepvad_forward_windows)
   const float* x;        // [B][ldx] (row stride ldx >= N: streaming windows are strided views)
   const float* window;   // [512]
   const float2* tw;      // [512] e^{-2 pi i m / 512}
-  float2* X;             // nullable [B][Tp][NBIN]
-  float2* Xout;          // nullable [B][NBIN][T] (debug entry)
+  float2* X;             // [B][Tp][NBIN]
+  void* unused0;         // unused padding that fixes the layout (without it hipcc pairs other kernarg loads: DESIGN.md §15a)
   float* specdb;         // nullable [B][Tp][SPEC_LD]
-  float* spec_out;       // nullable [B][NBIN][T] (debug entry)
-  // fused STFT + activity gate (k_stft_gate, the forward): window_db != window only when the checkpoint's
-  // spec_input and spec_output windows differ (then specdb keeps the dB spectrum for the side pass)
+  void* unused1;         // unused padding that fixes the layout, as unused0
+  // the dB spectrum's window: window_db != window only when the checkpoint's spec_input and spec_output windows
+  // differ (then specdb keeps the dB spectrum for the side pass)
   const float* window_db;
   int activity;
   const float* gate_w;   // activity_input.weight [9], bias [9], prelu [10]
   float* S0;             // [B][Tp][CH] gated bins 1..256 (TCN input)
   double* gate_rec;      // [B][Tp/GATE_ROWS][2] TCN.LN partial statistics
-  int db_out;            // k_stft_gate: also store the dB spectrum (specdb) when the windows are equal (test entry)
+  int db_out;            // also store the dB spectrum (specdb) when the windows are equal (test entry)
   unsigned long long* probe;  // nullable diagnostics (SEPVAD_TAIL_PROBE): [workgroups][8] phase stamps
 };
 hipError_t launch_stft_gate(const StftArgs& a, hipStream_t s);
@@ -182,7 +182,7 @@ struct VadFeatArgs {     // k_vad_feat: conv1_1 finish + BN_1 from the output he
   const float* vP;       // [B][2][Tp][HEAD_VAD_N]
   const float* b1; float alpha;       // conv1_1 bias [4], relu_1 PReLU
   const float* g; const float* be; float eps;  // BN_1 affine, eps
-  float* feat;           // [B][2][4][Tp] normalised features (the k_istft VAD tail's input)
+  float* feat;           // [B][2][4][Tp] normalised features (the input of k_istft_pair's VAD tail)
   double* out_rec;       // T > VF_ONE_T: [B*2][vf_nrec(Tp)][2] BN_1 partial records; feat is then un-normalised
 };
 // k_vad_feat finishes BN_1 itself up to VF_ONE_T frames (one workgroup per utterance and speaker); longer utterances run
@@ -192,10 +192,9 @@ __host__ __device__ inline int vf_nrec(int Tp) { return (Tp + VF_ROWS - 1) / VF_
 hipError_t launch_vad_feat(const VadFeatArgs& a, hipStream_t s);
 
 struct IstftArgs {
-  int BS, S, N, T, Tp, est_mode;  // est_mode 1: forward (mask X, VAD); 0: est given (debug entry)
+  int BS, N, T, Tp;      // BS = 2 B rows of y: both speakers of an utterance in one workgroup
   const float2* X;       // [B][Tp][NBIN]
   const float* masks;    // [B][Tp][MOUT_PAD] pre-sigmoid
-  const float2* est_in;  // [BS][NBIN][T] (est_mode 0)
   const float* window;   // [512]
   const float2* tw;      // [512]
   // VAD tail (model/model.py:160-179,444-457); has_vad = 0 -> no VAD, gain 1
@@ -541,9 +540,7 @@ struct MaskSideArgs {    // bin-major copies of the head output (side attributes
   float* mask;           // nullable [B][MOUT][T] sigmoid
 };
 hipError_t launch_mask_side(const MaskSideArgs& a, hipStream_t s);
-hipError_t launch_stft(const StftArgs& a, hipStream_t s);
 hipError_t launch_vad1(const Vad1Args& a, hipStream_t s);
-hipError_t launch_istft(const IstftArgs& a, hipStream_t s);
-hipError_t launch_istft_pair(const IstftArgs& a, hipStream_t s);  // the forward (est_mode 1, S = 2)
+hipError_t launch_istft_pair(const IstftArgs& a, hipStream_t s);
 
 }  // namespace sepvad

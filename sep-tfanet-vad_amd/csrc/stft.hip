@@ -46,7 +46,7 @@ __device__ __forceinline__ void rfft512_col(const float* xb, int s0base, int N, 
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int k1 = 1; k1 < 16; ++k1) {  // W256^(c k1) = W512^(2 c k1)
-    x[d16(k1)] = cmul(x[d16(k1)], twid<true>(tw, mul_late(c, 2 * k1)));
+    x[d16(k1)] = cmul(x[d16(k1)], twid(tw, mul_late(c, 2 * k1)));
     if (k1 % 4 == 3) {
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);

@@ -301,7 +301,7 @@ __device__ __forceinline__ float half_total(float v) {
   v += dpp_f<0x142>(v);
   return v;
 }
-// Lane exchanges of the recursive-halving reductions (spectral.hip k_vad1): swap lanes L <-> L ^ 16 (v_permlane16_swap)
+// Lane exchanges of the recursive-halving reductions (vad.hip k_vad1): swap lanes L <-> L ^ 16 (v_permlane16_swap)
 // or L <-> L ^ 32 (v_permlane32_swap) between two registers. Inline asm: this hipcc's builtin pair result came back as the
 // same register twice (tools/probe_src/halving.hip); "s_nop 1" covers the VALU-write -> permlane hazard.
 __device__ __forceinline__ void swap16(float& x, float& y) {

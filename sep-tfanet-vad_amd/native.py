@@ -97,8 +97,6 @@ _ABI = {
     "sepvad_stft_gate_test": (i32, (P, P, i32, i32, P, P, P)),
     "sepvad_istft_pair_test": (i32, (P, P, P, i32, i32, P, P, P)),
     "sepvad_set_tcn_dump": (i32, (P, P)),
-    "sepvad_stft": (i32, (P, P, i32, i32, P, P, P)),
-    "sepvad_istft": (i32, (P, P, i32, i32, P, P)),
     "sepvad_pit_l1": (i32, (P, i64, P, i64, i32, i64, P, P, P, P, P)),
     "sepvad_pit_l1_sums": (i32, (P, i64, P, i64, i32, i64, P, P, P)),
     "sepvad_pit_l1_choose": (i32, (P, dbl, i32, P, P, P, P)),
@@ -508,16 +506,6 @@ class Handle:
         v = buf[:, :, :T, :].permute(0, 1, 3, 2)
         return v[0], v[1], v[2]
 
-    def stft(self, x: torch.Tensor):
-        """STFT with DC zeroed and its dB spectrum (kernel-level test entry)."""
-        x = x.to(self.device, torch.float32).contiguous()
-        B, N = x.shape
-        T = 1 + N // 256
-        X = torch.empty(B, 257, T, device=self.device, dtype=torch.complex64)
-        spec = torch.empty(B, 257, T, device=self.device, dtype=torch.float32)
-        _check(self._lib.sepvad_stft(self._h, _ptr(x), B, N, _ptr(X), _ptr(spec), self._stream()), "sepvad_stft")
-        return X, spec
-
     def stft_fused(self, x: torch.Tensor):
         """The forward's own front end (k_stft_gate, sepvad_stft_gate_test): (X [B, 257, T] complex64 with DC
         zeroed, its dB spectrum [B, 257, T]) from the frame-major workspace layout."""
@@ -546,11 +534,3 @@ class Handle:
         _check(self._lib.sepvad_istft_pair_test(self._h, _ptr(Xf), _ptr(mf), B, N, _ptr(y), _ptr(est), self._stream()),
                "sepvad_istft_pair_test")
         return y, est
-
-    def istft(self, est: torch.Tensor, N: int):
-        """torch.istft(center=True, length=N) of est [BS, 257, T] complex64 (kernel-level test entry)."""
-        est = est.to(self.device, torch.complex64).contiguous()
-        BS = est.shape[0]
-        y = torch.empty(BS, N, device=self.device, dtype=torch.float32)
-        _check(self._lib.sepvad_istft(self._h, _ptr(est), BS, N, _ptr(y), self._stream()), "sepvad_istft")
-        return y

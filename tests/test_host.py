@@ -102,7 +102,7 @@ def test_ctypes_signatures_match_the_header():
     assert len(protos) == len(native.EXPORTED_SYMBOLS)  # a prototype the pattern misses fails here
     for s in native.EXPORTED_SYMBOLS:
         assert hasattr(lib, s), s
-    assert lib.sepvad_abi_version() == 1 == _header_constants()["SEPVAD_ABI_VERSION"]
+    assert lib.sepvad_abi_version() == 2 == _header_constants()["SEPVAD_ABI_VERSION"]
     for name, (ret, args) in protos.items():
         restype, argtypes = native._ABI[name]
         fn = getattr(lib, name)

@@ -1,7 +1,6 @@
-"""Float32 accuracy of the two 256-point complex FFT formulations used on the GPU, emulated in numpy
-(one rounding per operation, no FMA): the radix-4 Stockham ping-pong (spectral.hip fft256, the debug
-k_stft / k_istft path) and the register four-step 16 x 16 (fft_common.h dft16 + stft.hip / istft.hip),
-both against a float64 FFT on 2000 random frames. DESIGN.md section 4d.
+"""Float32 accuracy of the 256-point complex FFT used on the GPU, the register four-step 16 x 16 transform
+(fft_common.h dft16 + stft.hip / istft.hip), emulated in numpy (one rounding per operation, no FMA) against a
+float64 FFT on 2000 random frames. DESIGN.md section 4d.
 
 usage: python tools/fft_accuracy.py   (a few seconds on the CPU)
 """
@@ -13,22 +12,6 @@ z=(rng.standard_normal((NF,256))+1j*rng.standard_normal((NF,256))).astype(np.com
 ref=np.fft.fft(z.astype(np.complex128),axis=1)
 tw=np.exp(-2j*np.pi*np.arange(512)/512).astype(np.complex64)
 def cm(a,b): return (a*b).astype(np.complex64)
-def stockham(x):
-    x=x.copy()
-    for Ns in [1,4,16,64]:
-        out=np.empty_like(x)
-        for j in range(64):
-            k=j&(Ns-1)
-            v=[x[:,j+r*64] for r in range(4)]
-            if Ns>1:
-                for r in range(1,4):
-                    v[r]=cm(v[r],tw[2*((r*k*(64//Ns))&255)])
-            a0=v[0]+v[2]; a1=v[0]-v[2]; a2=v[1]+v[3]; a3=v[1]-v[3]
-            a3=(a3.imag-1j*a3.real).astype(np.complex64)
-            idx=(j//Ns)*Ns*4+k
-            out[:,idx]=a0+a2; out[:,idx+Ns]=a1+a3; out[:,idx+2*Ns]=a0-a2; out[:,idx+3*Ns]=a1-a3
-        x=out
-    return x
 C1=f32(0.9238795042037964); S1=f32(0.3826834261417389); R=f32(0.7071067690849304)
 W16={1:(C1,S1),2:(R,R),3:(S1,C1),6:(-R,R),9:(-C1,-S1)}
 def dft4(v0,v1,v2,v3):
@@ -67,7 +50,5 @@ def fourstep(z):
         x=dft16(x)
         for k2 in range(16): out[:,k1+16*k2]=x[d16(k2)]
     return out
-for name,fn in [("stockham",stockham),("fourstep",fourstep)]:
-    y=fn(z)
-    e=np.abs(y-ref)
-    print(name, "max abs err", e.max(), "rms", np.sqrt((e**2).mean()))
+e=np.abs(fourstep(z)-ref)
+print("fourstep max abs err", e.max(), "rms", np.sqrt((e**2).mean()))
