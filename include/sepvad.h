@@ -293,7 +293,8 @@ int32_t sepvad_si_sdr(const float* P, int64_t p_ld, const float* Tg, int64_t t_l
 int32_t sepvad_snr(const float* P, int64_t p_ld, const float* Tg, int64_t t_ld, int64_t N, int32_t R,
                    const int32_t* pidx, const int32_t* tidx, int32_t zero_mean, float* out, void* stream);
 
-/* ---- STOI (model/stoi_metric.py:207-301 stoi, extended=False; model/metric.py:207-223 Stoi) ----------
+/* ---- STOI (model/stoi_metric.py:207-301 stoi, extended=False; model/metric.py:207-223 Stoi; the extended
+ * form follows below) ----------
  * HOST function, no GPU needed: the design the device path uses for signals sampled at fs_sig (8000, 10000 or
  * 16000 Hz). taps (capacity `cap` floats) receive the resampling window h / sum(h) of _resample_window_oct and
  * resample_oct (stoi_metric.py:11-52), computed in double and rounded to float: 581 taps at 16 kHz (5/8), 365 at
@@ -321,6 +322,37 @@ int64_t sepvad_stoi_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig);
 int32_t sepvad_stoi(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, int64_t N, int32_t R,
                     const int32_t* xidx, const int32_t* yidx, int32_t fs_sig, void* scratch, int64_t scratch_bytes,
                     double* out, int32_t* frames, void* stream);
+
+/* ---- Extended STOI (ESTOI; stoi(x, y, fs_sig, extended=True), stoi_metric.py:177-193,268-271) ----------
+ * modes of the two entries below: a bit mask of the results asked for. */
+#define SEPVAD_STOI_CLASSIC 1
+#define SEPVAD_STOI_EXTENDED 2
+
+/* HOST function: bytes of device scratch sepvad_stoi_ex needs: with SEPVAD_STOI_CLASSIC alone the size of the
+ * classic query above, with SEPVAD_STOI_EXTENDED that plus one double per pair and chunk of 64 segments. Negative
+ * status as above, and if modes is outside 1..3. */
+int64_t sepvad_stoi_ex_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig, int32_t modes);
+
+/* sepvad_stoi's arguments plus modes: the front end (resampling, silence removal, spectra, band magnitudes) runs once,
+ * then the correlation stage of every mode asked for. out_stoi[r] (SEPVAD_STOI_CLASSIC) has the bits sepvad_stoi
+ * gives: it is the same launches. out_estoi[r] (SEPVAD_STOI_EXTENDED) is extended STOI: for every window j of 30
+ * spectra and each signal, the 15 x 30 block of band magnitudes has the mean over its 30 frames subtracted from every
+ * band row and the row divided by its norm, then the mean over its 15 bands subtracted from every frame column and
+ * the column divided by its norm; out_estoi[r] = sum over windows, bands and frames of the product of the two
+ * signals' blocks / (30 J), J = M - 29 windows. The reference adds 2.2e-16 * randn noise before each centring; that
+ * term is left out (it moves the reference's value by 1e-15 where the value does not depend on the draw).
+ * Degenerate rule: a row or column whose norm is zero becomes a row or column of zeros (the reference normalises
+ * its noise there, so its value is a random draw), and an all-zero estimate scores exactly 0.0, as with classic STOI.
+ * Zero includes the rounding remainder of an exact zero: a row norm up to 2^-40 sqrt(30) times the row's mean (30
+ * equal magnitudes) and a column norm up to 2^-40 (15 unit-norm rows that agree in that frame); dividing by such a
+ * norm would turn rounding into a unit vector. M < 30 stores exactly 1e-5. All in double; every sum has a fixed order that depends on the pair
+ * alone (no atomics): the result is bitwise independent of R, of the other pairs and of repeated runs.
+ * An output pointer that is missing for a requested mode is SEPVAD_E_ARG; one for a mode not requested is ignored.
+ * frames nullable. Every refusal (null pointers, x_ld / y_ld < N, rate, shape, modes, scratch size or alignment)
+ * is made on the host before any device call. */
+int32_t sepvad_stoi_ex(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, int64_t N, int32_t R,
+                       const int32_t* xidx, const int32_t* yidx, int32_t fs_sig, void* scratch, int64_t scratch_bytes,
+                       int32_t modes, double* out_stoi, double* out_estoi, int32_t* frames, void* stream);
 
 /* Replaces Accuracy_Vad()(preds, targets, _) (model/metric.py:163-177): labels = preds > 0.5 (NaN kept),
  * written back into preds when in_place (the reference masks its argument in place); out[0] = fraction of

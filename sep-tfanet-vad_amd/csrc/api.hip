@@ -476,6 +476,44 @@ int32_t sepvad_stoi(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, 
   HIPRET(launch_stoi(a, (hipStream_t)stream));
 }
 
+static_assert(STOI_MODE_CLASSIC == SEPVAD_STOI_CLASSIC && STOI_MODE_EXTENDED == SEPVAD_STOI_EXTENDED, "sepvad.h");
+static bool stoi_modes_ok(int32_t modes) { return modes >= 1 && modes <= (SEPVAD_STOI_CLASSIC | SEPVAD_STOI_EXTENDED); }
+
+int64_t sepvad_stoi_ex_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig, int32_t modes) {
+  StoiDesign d;
+  if (!stoi_design(fs_sig, d))
+    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex_scratch_bytes: fs_sig must be 8000, 10000 or 16000");
+  if (!stoi_modes_ok(modes)) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex_scratch_bytes: modes must be 1, 2 or 3");
+  if (!stoi_shape_ok(R, N, d.up, d.down))
+    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex_scratch_bytes: need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
+  return stoi_ex_scratch_layout(R, N, d.up, d.down, modes, nullptr, nullptr);
+}
+
+int32_t sepvad_stoi_ex(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, int64_t N, int32_t R,
+                       const int32_t* xidx, const int32_t* yidx, int32_t fs_sig, void* scratch, int64_t scratch_bytes,
+                       int32_t modes, double* out_stoi, double* out_estoi, int32_t* frames, void* stream) {
+  if (!X || !Y || !scratch || N < 1 || x_ld < N || y_ld < N) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: bad arguments");
+  if (!stoi_modes_ok(modes)) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: modes must be 1, 2 or 3");
+  if (((modes & SEPVAD_STOI_CLASSIC) && !out_stoi) || ((modes & SEPVAD_STOI_EXTENDED) && !out_estoi))
+    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: a requested mode has no output pointer");
+  // every refusal comes before the first HIP call (stoi_tables uploads the design): the host design gives up / down
+  StoiDesign d;
+  if (!stoi_design(fs_sig, d)) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: fs_sig must be 8000, 10000 or 16000");
+  if (!stoi_shape_ok(R, N, d.up, d.down))
+    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
+  if (scratch_bytes < stoi_ex_scratch_layout(R, N, d.up, d.down, modes, nullptr, nullptr))
+    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: scratch too small (sepvad_stoi_ex_scratch_bytes)");
+  if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: scratch must be 256-byte aligned");
+  StoiArgs a{};
+  HIPCHK(stoi_tables(fs_sig, a));
+  stoi_ex_scratch_layout(R, N, a.up, a.down, modes, &a, (char*)scratch);
+  a.X = X; a.x_ld = x_ld; a.Y = Y; a.y_ld = y_ld; a.xidx = xidx; a.yidx = yidx; a.N = N; a.R = R;
+  a.out = (modes & SEPVAD_STOI_CLASSIC) ? out_stoi : nullptr;
+  a.out_ex = (modes & SEPVAD_STOI_EXTENDED) ? out_estoi : nullptr;
+  a.frames = frames;
+  HIPRET(launch_stoi_ex(a, modes, (hipStream_t)stream));
+}
+
 int32_t sepvad_vad_accuracy(float* preds, const float* targets, int32_t B, int32_t S, int32_t T, int32_t in_place,
                             float* out, void* stream) {
   if (!preds || !targets || !out || B < 1 || S < 1 || S > VACC_MAX_S || T < 1)

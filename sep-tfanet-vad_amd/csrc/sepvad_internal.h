@@ -317,8 +317,13 @@ struct StoiArgs {
   int* nkept;                       // [R]
   double* tob;                      // [R][2][15][nF] third-octave magnitudes of spectrum m
   double* out; int* frames;         // [R]; frames nullable
+  double* out_ex;                   // [R] extended STOI (launch_stoi_ex with STOI_MODE_EXTENDED)
+  double* ex_part; int ex_nchunk;   // [R][ex_nchunk] chunk partials of the extended correlation (scratch)
 };
+constexpr int STOI_MODE_CLASSIC = 1, STOI_MODE_EXTENDED = 2;  // SEPVAD_STOI_CLASSIC / _EXTENDED (api.hip asserts)
 long long stoi_scratch_layout(int R, long long N, int up, int down, StoiArgs* a, char* base);  // bytes
+long long stoi_ex_scratch_layout(int R, long long N, int up, int down, int modes, StoiArgs* a, char* base);
+hipError_t launch_stoi_ex(const StoiArgs& a, int modes, hipStream_t s);
 hipError_t stoi_tables(int fs_sig, StoiArgs& a);  // device-resident taps / window / twiddles of the current device
 hipError_t launch_stoi(const StoiArgs& a, hipStream_t s);
 constexpr int VACC_MAX_S = 8;

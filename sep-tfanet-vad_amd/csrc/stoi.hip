@@ -13,6 +13,14 @@
 //                    tob = sqrt(sum |X|^2) of the 15 bands. M = K - 1 spectra (exclusive end).
 //   k_stoi_corr      (:262-300) every band x window of 30 frames: normalise, clip, centre, correlate; d = sum / (15 J).
 //                    M < 30 gives exactly 1e-5 (:251-256).
+// Extended STOI (ESTOI, extended=True, :177-193,268-271) shares stages 1 to 4 and replaces the last one:
+//   k_stoi_ex_corr   every window of 30 frames of both signals: rows (bands) mean- and norm-normalised over the 30
+//                    frames, then columns (frames) over the 15 bands, then the sum of products. The reference adds
+//                    EPS * randn before each centring; that term is left out here (it moves the value by 1e-15 where
+//                    the value is defined at all). A row or column whose norm is zero, exactly or up to the rounding
+//                    of its centring (st_ex_normalize), becomes zeros (the reference normalises pure noise there: a
+//                    random draw), so an all-zero estimate scores exactly 0.
+//   k_stoi_ex_finish adds the per-chunk partials of a pair in order: d = sum / (30 J); 1e-5 where M < 30.
 // Everything after the float store of the resampled signal is double: the work is a few MFLOP per pair, far below what
 // the traffic costs, and it keeps the result within rounding of the reference's float64 numpy chain. Every reduction
 // has a fixed order that depends on the pair alone (bitwise reproducible, independent of R and of the batch).
@@ -245,6 +253,137 @@ __global__ __launch_bounds__(ST_THREADS) void k_stoi_corr(StoiArgs a, double cli
   if (t == 0) a.out[r] = sum / ((double)J * STOI_BANDS);
 }
 
+// ---- extended correlation -------------------------------------------------------------------------------------
+// Grid (segment chunks, R). A workgroup owns ST_EX_CHUNK consecutive segments of one pair and stages the
+// 15 x (ST_EX_CHUNK + 29) magnitudes of both signals they cover in LDS once (each is used by up to 30 segments).
+// A half-wave owns a segment: lane i < 30 holds frame i, the 15 bands in registers. Row statistics (over frames) are
+// xor-butterfly sums inside the half-wave, which give every lane the same bits; column statistics (over bands) are
+// in-lane loops. Half-wave h takes segments h, h + 8, ... of the chunk in order; lanes, half-waves and chunks are
+// then added in a fixed order that depends on the pair's J alone.
+constexpr int ST_EX_CHUNK = 64;
+constexpr int ST_EX_HW = ST_THREADS / 32;                     // half-waves per workgroup
+constexpr int ST_EX_TILE = ST_EX_CHUNK + STOI_SEG - 1;        // 93 frames: an odd stride in doubles
+static_assert(ST_EX_CHUNK % ST_EX_HW == 0, "every half-wave runs the same number of rounds");
+
+// Sum over the 32 lanes of a half-wave, the same bits in every lane. A segment needs 60 of these per signal pair, and
+// __shfl_xor goes through the LDS crossbar (ds_bpermute, two per double), which then paces the kernel; four of the five
+// steps stay in the VALU as DPP moves: lanes 1 and 2 apart by quad permutes, then, every quad being uniform, the
+// other quad of 8 through row_half_mirror and the other 8 of 16 through row_mirror. Only the step across the two rows
+// of 16 takes a swizzle. Each step adds two values in both orders, so partners end with equal bits.
+template <int CTRL>
+__device__ __forceinline__ double st_dpp(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double st_half_sum(double v) {  // all 64 lanes of the wave take part
+  // plain additions: fused with the caller's product, fma(c, c, partner's rounded square) would differ between partners
+#pragma clang fp contract(off)
+  v += st_dpp<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  v += st_dpp<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  v += st_dpp<0x141>(v);  // row_half_mirror: lane 7 - i of each 8
+  v += st_dpp<0x140>(v);  // row_mirror: lane 15 - i of each 16
+  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), 0x401F);  // lane i ^ 16 of each 32
+  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), 0x401F);
+  return v + __hiloint2double(hi, lo);
+}
+
+// Degenerate rule: a row or column whose norm is zero becomes zeros. "Zero" includes what rounding leaves of an exact
+// zero: a row of 30 equal magnitudes centres to at most a few ulp of its mean, and a column whose 15 unit-norm rows
+// agree in that frame (a window in which the estimate has one non-zero frame: every row is the same indicator
+// pattern) centres to at most 15 ulp of 1. Dividing such a remainder by its norm would turn rounding into a unit
+// vector, so a row with norm <= 2^-40 sqrt(30) mean and a column with norm <= 2^-40 are zeros as well: 2^-40 is
+// 2^12 ulp of the scale, two orders above any such remainder, and a row or column that small carries no more
+// than 12 significant bits of signal after centring.
+constexpr double ST_EX_TOL2 = 0x1p-80;  // (2^-40)^2
+
+// v[b] = magnitude of band b at this lane's frame (0 on lanes that hold no frame) -> row and column normalised
+__device__ __forceinline__ void st_ex_normalize(double (&v)[STOI_BANDS], bool active) {
+#pragma unroll
+  for (int b = 0; b < STOI_BANDS; ++b) {
+    const double mean = st_half_sum(v[b]) / STOI_SEG;
+    const double c = active ? v[b] - mean : 0.0;
+    const double ss = st_half_sum(c * c);
+    const double inv = ss > (ST_EX_TOL2 * STOI_SEG) * (mean * mean) ? 1.0 / sqrt(ss) : 0.0;  // zero-norm row -> zeros
+    v[b] = c * inv;
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int b = 0; b < STOI_BANDS; ++b) sum += v[b];
+  const double mean = sum / STOI_BANDS;
+  double ss = 0.0;
+#pragma unroll
+  for (int b = 0; b < STOI_BANDS; ++b) {
+    v[b] -= mean;
+    ss += v[b] * v[b];
+  }
+  const double inv = ss > ST_EX_TOL2 ? 1.0 / sqrt(ss) : 0.0;  // zero-norm column -> zeros
+#pragma unroll
+  for (int b = 0; b < STOI_BANDS; ++b) v[b] *= inv;
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stoi_ex_corr(StoiArgs a) {
+  __shared__ double tile[2][STOI_BANDS][ST_EX_TILE];
+  __shared__ double red[ST_EX_HW];
+  const int r = blockIdx.y, t = threadIdx.x;
+  const int M = a.nkept[r] - 1;
+  const int J = M - STOI_SEG + 1;
+  const long long j0 = (long long)blockIdx.x * ST_EX_CHUNK;
+  if (j0 >= J) return;  // the whole workgroup (also M < 30)
+  const int nseg = (int)min((long long)ST_EX_CHUNK, J - j0);
+  const int nfr = nseg + STOI_SEG - 1;  // j0 + nfr <= M <= nF - 1: inside the pair's rows of tob
+  for (int it = t; it < 2 * STOI_BANDS * ST_EX_TILE; it += ST_THREADS) {
+    const int sb = it / ST_EX_TILE, f = it - sb * ST_EX_TILE;
+    (&tile[0][0][0])[it] = f < nfr ? a.tob[((size_t)r * 2 * STOI_BANDS + sb) * a.nF + j0 + f] : 0.0;
+  }
+  __syncthreads();
+  const int h = t >> 5, i = t & 31;
+  const bool lane = i < STOI_SEG;
+  double acc = 0.0;
+  for (int k = 0; k < ST_EX_CHUNK / ST_EX_HW; ++k) {
+    const int j = h + k * ST_EX_HW;                 // segment of the chunk; frame j + i <= 63 + 29 stays in the tile
+    if ((j & ~1) >= nseg) break;                    // wave-uniform: both of the wave's segments are past the end
+    const bool active = lane && j < nseg;           // a segment past the end contributes exact zeros
+    const int f = active ? j + i : 0;
+    double x[STOI_BANDS], y[STOI_BANDS];
+#pragma unroll
+    for (int b = 0; b < STOI_BANDS; ++b) {
+      x[b] = active ? tile[0][b][f] : 0.0;
+      y[b] = active ? tile[1][b][f] : 0.0;
+    }
+    st_ex_normalize(x, active);
+    st_ex_normalize(y, active);
+    double p = 0.0;
+#pragma unroll
+    for (int b = 0; b < STOI_BANDS; ++b) p += x[b] * y[b];
+    acc += p;
+  }
+  acc = st_half_sum(acc);
+  if (i == 0) red[h] = acc;
+  __syncthreads();
+  if (t == 0) {
+    double s = 0.0;
+    for (int q = 0; q < ST_EX_HW; ++q) s += red[q];
+    a.ex_part[(size_t)r * a.ex_nchunk + blockIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stoi_ex_finish(StoiArgs a) {
+  __shared__ double red[16];
+  const int r = blockIdx.x, t = threadIdx.x;
+  const int M = a.nkept[r] - 1;
+  if (t == 0 && a.frames) a.frames[r] = M;
+  if (M < STOI_SEG) {
+    if (t == 0) a.out_ex[r] = 1e-5;
+    return;
+  }
+  const int J = M - STOI_SEG + 1, nc = (J + ST_EX_CHUNK - 1) / ST_EX_CHUNK;  // <= ex_nchunk
+  double acc = 0.0;
+  for (int c = t; c < nc; c += ST_THREADS) acc += a.ex_part[(size_t)r * a.ex_nchunk + c];
+  const double sum = block_sum(acc, red);
+  if (t == 0) a.out_ex[r] = sum / ((double)J * STOI_SEG);
+}
+
 static size_t st_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 long long stoi_scratch_layout(int R, long long N, int up, int down, StoiArgs* a, char* base) {
@@ -264,6 +403,23 @@ long long stoi_scratch_layout(int R, long long N, int up, int down, StoiArgs* a,
     a->kept = reinterpret_cast<int*>(base + o_kept);
     a->nkept = reinterpret_cast<int*>(base + o_nkept);
     a->tob = reinterpret_cast<double*>(base + o_tob);
+  }
+  return (long long)off;
+}
+
+// The classic layout, then (modes & STOI_MODE_EXTENDED) the chunk partials [R][ex_nchunk] of k_stoi_ex_corr, sized
+// for every frame kept like the rest.
+long long stoi_ex_scratch_layout(int R, long long N, int up, int down, int modes, StoiArgs* a, char* base) {
+  size_t off = (size_t)stoi_scratch_layout(R, N, up, down, a, base);
+  if (modes & STOI_MODE_EXTENDED) {
+    const long long nF = stoi_num_frames(stoi_resampled_len(N, up, down));
+    const long long J = std::max(1LL, nF - 1 - (STOI_SEG - 1));
+    const long long nc = (J + ST_EX_CHUNK - 1) / ST_EX_CHUNK;
+    if (a) {
+      a->ex_nchunk = (int)nc;
+      a->ex_part = reinterpret_cast<double*>(base + off);
+    }
+    off = st_align(off + (size_t)R * nc * sizeof(double));
   }
   return (long long)off;
 }
@@ -304,7 +460,8 @@ hipError_t stoi_tables(int fs_sig, StoiArgs& a) {
   return hipSuccess;
 }
 
-hipError_t launch_stoi(const StoiArgs& a, hipStream_t s) {
+// stages 1 to 4: everything up to the band magnitudes
+static hipError_t launch_stoi_front(const StoiArgs& a, hipStream_t s) {
   if (a.R < 1 || a.R > 65535 || a.nF < 1 || a.L <= STOI_FRAME) return hipErrorInvalidValue;
   hipError_t e;
   if (a.up != a.down) {
@@ -322,9 +479,36 @@ hipError_t launch_stoi(const StoiArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_stoi_spec, dim3(a.nF - 1, a.R), dim3(ST_THREADS), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
+  return hipSuccess;
+}
+
+static hipError_t launch_stoi_classic(const StoiArgs& a, hipStream_t s) {
   const double clip1 = 1.0 + std::pow(10.0, -STOI_BETA / 20.0);
   hipLaunchKernelGGL(k_stoi_corr, dim3(a.R), dim3(ST_THREADS), 0, s, a, clip1);
   return hipGetLastError();
+}
+
+hipError_t launch_stoi(const StoiArgs& a, hipStream_t s) {
+  const hipError_t e = launch_stoi_front(a, s);
+  return e != hipSuccess ? e : launch_stoi_classic(a, s);
+}
+
+// modes: STOI_MODE_CLASSIC (a.out) | STOI_MODE_EXTENDED (a.out_ex, a.ex_part); the classic result comes from the
+// launches of launch_stoi
+hipError_t launch_stoi_ex(const StoiArgs& a, int modes, hipStream_t s) {
+  hipError_t e = launch_stoi_front(a, s);
+  if (e != hipSuccess) return e;
+  if (modes & STOI_MODE_CLASSIC) {
+    if ((e = launch_stoi_classic(a, s)) != hipSuccess) return e;
+  }
+  if (modes & STOI_MODE_EXTENDED) {
+    if (a.ex_nchunk < 1 || !a.ex_part || !a.out_ex) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_stoi_ex_corr, dim3(a.ex_nchunk, a.R), dim3(ST_THREADS), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_stoi_ex_finish, dim3(a.R), dim3(ST_THREADS), 0, s, a);
+    return hipGetLastError();
+  }
+  return hipSuccess;
 }
 
 }  // namespace sepvad

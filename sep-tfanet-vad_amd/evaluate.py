@@ -154,7 +154,7 @@ def simple_vad(masks, perm=None):
     return simple
 
 
-def score_batch(sep, target, mix=None, vad=None, labels=None, masks=None, sdr_type="sisdr"):
+def score_batch(sep, target, mix=None, vad=None, labels=None, masks=None, sdr_type="sisdr", stoi_fs=None):
     """One test.py step (test.py:129-181) for a batch: sep, target [B, 2, N]; mix [B, N]; vad, labels [B, 2, T];
     post-sigmoid masks [B, 2, 257, T]. Returns a dict of device tensors:
 
@@ -162,7 +162,11 @@ def score_batch(sep, target, mix=None, vad=None, labels=None, masks=None, sdr_ty
       (with mix) si_sdri;
     * sep_reordered [B, 2, N] = reorder_source_mse(sep, perm);
     * with vad and labels, of ``eval_vad`` under that perm: bce_rows, bce_mean, pw_ce, conf, labels; with masks as
-      well simple_vad and conf_simple; with masks alone simple_vad.
+      well simple_vad and conf_simple; with masks alone simple_vad;
+    * with stoi_fs (the waveforms' sampling rate: 8000, 10000 or 16000), the columns the reference's post-processing
+      reads: stoi and estoi [B, 2] float64 (target j against the estimate perm assigns to it) and, with mix,
+      initial_stoi and initial_estoi (target j against the mixture), all from one sepvad_stoi_ex call. Without
+      stoi_fs the result is what it was before the argument existed.
 
     Launches: sepvad_eval_separation, the reordering copy (sepvad_stream_append) and, with a VAD track or masks,
     sepvad_eval_vad; nothing is synchronised and no index tensor is built on the host (perm stays on the device)."""
@@ -179,4 +183,30 @@ def score_batch(sep, target, mix=None, vad=None, labels=None, masks=None, sdr_ty
         out.update(eval_vad(vad, labels, out["perm"], masks))
     elif masks is not None:
         out["simple_vad"] = simple_vad(masks, out["perm"])
+    if stoi_fs is not None:
+        out.update(_stoi_columns(sep, target, mix, out["perm"], stoi_fs))
     return out
+
+
+def _stoi_columns(sep, target, mix, perm, fs_sig):
+    """stoi / estoi [B, 2] (target j against the estimate perm assigns to it) and, with mix, initial_stoi /
+    initial_estoi (target j against the mixture), float64, from one sepvad_stoi_ex call over 2B or 4B pairs. The pairs
+    are addressed by row indices computed from perm on the device; with mix the estimate rows and the mixtures are
+    first joined into one [3B, N] buffer (one base pointer per side), in their own order."""
+    from . import metrics
+    B, _, N = sep.shape
+    dev = sep.device
+    X = target.to(torch.float32).reshape(2 * B, N).contiguous()
+    Y = sep.to(torch.float32).reshape(2 * B, N).contiguous()
+    rows = torch.arange(2 * B, device=dev, dtype=torch.int64)
+    yidx = (rows // 2) * 2 + perm.reshape(-1)
+    xidx = rows
+    if mix is not None:
+        Y = torch.cat([Y, mix.to(torch.float32).reshape(B, N)])
+        xidx = torch.cat([rows, rows])
+        yidx = torch.cat([yidx, 2 * B + rows // 2])
+    d, e, _ = metrics.stoi_both_pairs(X, Y, fs_sig, xidx.to(torch.int32), yidx.to(torch.int32))
+    res = dict(stoi=d[:2 * B].reshape(B, 2), estoi=e[:2 * B].reshape(B, 2))
+    if mix is not None:
+        res.update(initial_stoi=d[2 * B:].reshape(B, 2), initial_estoi=e[2 * B:].reshape(B, 2))
+    return res

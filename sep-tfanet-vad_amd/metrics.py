@@ -15,8 +15,11 @@
 * ``signal_noise_ratio`` (``model/metric.py:104-143``) and ``pit_snr`` (``:255-256``): the SNR of the same row
   pairs (``k_snr``, the moments of ``k_si_sdr`` with another closed form) and the PIT reduction over it.
 * ``stoi`` (``model/stoi_metric.py:207-301``, classic STOI; ``extended=True`` draws ``np.random`` noise and is
-  refused), the ``Stoi`` module and ``stoi_met`` (``model/metric.py:207-223,276-277``): every pair of a batch in one
-  call of ``sepvad_stoi`` (csrc/stoi.hip), float64 results on the device, no host round trip.
+  refused there: see ``estoi``), the ``Stoi`` module and ``stoi_met`` (``model/metric.py:207-223,276-277``): every
+  pair of a batch in one call of ``sepvad_stoi`` (csrc/stoi.hip), float64 results on the device, no host round trip.
+* ``estoi``, ``Estoi`` and ``estoi_met``: extended STOI (``stoi_metric.py:177-193,268-271``) with the reference's
+  random term left out (it moves the reference's value by 1e-15) and zero-norm rows and columns set to zero;
+  ``estoi_pairs`` and ``stoi_both_pairs`` (both metrics from one ``sepvad_stoi_ex`` call) are the row-pair forms.
 * ``pit_CE_vad`` (``model/metric.py:264-265``), ``vad_confusion`` (the per-speaker ``confusion_matrix`` of
   ``test.py:164``) and ``calc_vad`` (``Our_utils/utils_test.py:67-73``): ``sepvad_eval_vad`` (csrc/eval.hip);
   ``evaluate.score_batch`` returns all of a ``test.py`` step's numbers from one pass over the rows.
@@ -169,16 +172,65 @@ def stoi_pairs(X, Y, fs_sig, xidx=None, yidx=None):
     return out, frames
 
 
+STOI_CLASSIC, STOI_EXTENDED = 1, 2  # SEPVAD_STOI_* (include/sepvad.h): the modes of sepvad_stoi_ex
+
+
+def _stoi_ex(X, Y, fs_sig, xidx, yidx, modes):
+    """sepvad_stoi_ex on 2-D contiguous float32 device rows: (stoi or None, estoi or None, M). xidx / yidx: a list
+    or a device int tensor (used as it is: no host round trip)."""
+    lib = _native.load_library()
+    if X.shape[1] != Y.shape[1]:
+        raise RuntimeError(f"x and y should have the same length, found {X.shape[1]} and {Y.shape[1]}")
+    N = X.shape[1]
+    R = len(xidx) if xidx is not None else X.shape[0]
+    dev = X.device
+    scratch = _native.scratch(dev, _native.query_bytes(lib.sepvad_stoi_ex_scratch_bytes,
+                                                       "sepvad_stoi_ex_scratch_bytes", R, N, int(fs_sig), modes))
+    d = torch.empty(R, device=dev, dtype=torch.float64) if modes & STOI_CLASSIC else None
+    e = torch.empty(R, device=dev, dtype=torch.float64) if modes & STOI_EXTENDED else None
+    frames = torch.empty(R, device=dev, dtype=torch.int32)
+    xi = torch.as_tensor(xidx, dtype=torch.int32, device=dev).contiguous() if xidx is not None else None
+    yi = torch.as_tensor(yidx, dtype=torch.int32, device=dev).contiguous() if yidx is not None else None
+    rc = lib.sepvad_stoi_ex(_native.ptr(X), X.shape[1], _native.ptr(Y), Y.shape[1], N, R, _native.ptr(xi),
+                            _native.ptr(yi), int(fs_sig), _native.ptr(scratch), scratch.numel(), modes,
+                            _native.ptr(d), _native.ptr(e), _native.ptr(frames), _native.stream_ptr(dev))
+    _native.check(rc, "sepvad_stoi_ex")
+    return d, e, frames
+
+
+def estoi_pairs(X, Y, fs_sig, xidx=None, yidx=None):
+    """Extended STOI of clean rows X[xidx[r]] vs estimate rows Y[yidx[r]], the arguments of ``stoi_pairs``. Returns
+    (d [R] float64, M [R] int32); d is exactly 1e-5 where M < 30 and exactly 0 for an all-zero estimate."""
+    _, e, frames = _stoi_ex(X, Y, fs_sig, xidx, yidx, STOI_EXTENDED)
+    return e, frames
+
+
+def stoi_both_pairs(X, Y, fs_sig, xidx=None, yidx=None):
+    """(stoi [R], estoi [R], M [R]) from one sepvad_stoi_ex call: the front end runs once. The classic values have
+    the bits of ``stoi_pairs``, the extended ones those of ``estoi_pairs``."""
+    return _stoi_ex(X, Y, fs_sig, xidx, yidx, STOI_CLASSIC | STOI_EXTENDED)
+
+
 def stoi(x: torch.Tensor, y: torch.Tensor, fs_sig: int, extended: bool = False):
     """model/stoi_metric.py:207-301 with the reference's argument order (x clean, y processed): [..., time] ROCm
-    tensors -> [...] float64 on the device."""
+    tensors -> [...] float64 on the device. ``extended=True`` is refused here; ``estoi`` is the native form."""
     if extended:
-        raise NotImplementedError("extended STOI adds np.random noise in the reference (stoi_metric.py:177-193) "
-                                  "and is not provided")
+        raise NotImplementedError("stoi(..., extended=True) adds np.random noise in the reference "
+                                  "(stoi_metric.py:177-193) and is not reproduced; use metrics.estoi, the same "
+                                  "formula with the random term left out")
     if x.shape != y.shape:
         raise RuntimeError(f"x and y should have the same length, found {tuple(x.shape)} and {tuple(y.shape)}")
     X, Y = _as_rows(x), _as_rows(y)
     return stoi_pairs(X, Y, fs_sig)[0].reshape(x.shape[:-1])
+
+
+def estoi(x: torch.Tensor, y: torch.Tensor, fs_sig: int):
+    """Extended STOI (stoi_metric.py:207-301 with extended=True, its random term left out) with ``stoi``'s argument
+    order (x clean, y processed): [..., time] ROCm tensors -> [...] float64 on the device."""
+    if x.shape != y.shape:
+        raise RuntimeError(f"x and y should have the same length, found {tuple(x.shape)} and {tuple(y.shape)}")
+    X, Y = _as_rows(x), _as_rows(y)
+    return estoi_pairs(X, Y, fs_sig)[0].reshape(x.shape[:-1])
 
 
 class Stoi(torch.nn.Module):
@@ -197,6 +249,23 @@ class Stoi(torch.nn.Module):
 
 stoi_met = Stoi()
 stoi_met.__name__ = "stoi_metric"
+
+
+class Estoi(torch.nn.Module):
+    """``Stoi`` with extended STOI: preds, targets [B, num_spk, time] -> mean ESTOI over [B, num_spk] (0-dim float64
+    device tensor)."""
+
+    def __init__(self, fs_sig: int = 16000):
+        super().__init__()
+        self.fs_sig = fs_sig
+
+    def forward(self, preds, targets, batch_indices_separation=None):
+        _check_same_shape(preds, targets)
+        return estoi(targets, preds, self.fs_sig).mean()
+
+
+estoi_met = Estoi()
+estoi_met.__name__ = "estoi_metric"
 
 
 class SI_SDRi(torch.nn.Module):

@@ -110,6 +110,8 @@ _ABI = {
     "sepvad_stoi_filter": (i32, (i32, P, i32, P)),
     "sepvad_stoi_scratch_bytes": (i64, (i32, i64, i32)),
     "sepvad_stoi": (i32, (P, i64, P, i64, i64, i32, P, P, i32, P, i64, P, P, P)),
+    "sepvad_stoi_ex_scratch_bytes": (i64, (i32, i64, i32, i32)),
+    "sepvad_stoi_ex": (i32, (P, i64, P, i64, i64, i32, P, P, i32, P, i64, i32, P, P, P, P)),
     "sepvad_vad_accuracy": (i32, (P, P, i32, i32, i32, i32, P, P)),
     "sepvad_eval_scratch_bytes": (i64, (i32, i64)),
     "sepvad_eval_separation": (i32, (P, i64, P, i64, P, i64, i32, i64, i32, i32, i32, dbl, P, i64, P, P, P, P, P, P)),
