@@ -498,6 +498,35 @@ int32_t sepvad_tail_backward(sepvad_handle h, const float* x, int64_t ldx, const
                              int64_t gv_b, int64_t gv_s, int64_t gv_t, const double* vadw, void* scratch,
                              int64_t scratch_bytes, float* g_masks, double* gpar, void* stream);
 
+/* ---- the output head with a backward (model/model.py:322-325,357) --------------------------------------
+ * TCN.output = PReLU -> GroupNorm(1, 256, eps 1e-5) -> weight-normed Conv1d(256 -> 514, 1): from the trunk output y
+ * [B][256][T] to masks_b [B][514][T] (both bin-major, as torch holds them), and loss.backward() through it: the stage
+ * behind sepvad_tail_backward's g_masks (csrc/head_grad.hip). The entries take plain device pointers: no
+ * handle, no allocation, no host synchronisation, nothing a forward left behind. hpar and gpar are
+ * SEPVAD_HEAD_NPAR device doubles: the folded conv weight v g / |v| [514][256] | its bias [514] | GroupNorm weight [256] |
+ * GroupNorm bias [256] | the PReLU slope. The fold and the weight-norm Jacobian are the caller's, in double. */
+enum { SEPVAD_HEAD_NPAR = 132611 };
+
+/* Device bytes of scratch (256-byte aligned) that sepvad_head_forward and sepvad_head_backward need for B utterances of
+ * T frames; negative status for B < 1, B > 32767, T < 2 or T > 2^20. */
+int64_t sepvad_head_scratch_bytes(int32_t B, int32_t T);
+
+/* masks_b [B][514][T] = W z + bias with z = GroupNorm(PReLU(y)). The product runs on fp32 MFMA in fp32 chains of 16 terms
+ * that are combined in double; the statistics and z are double arithmetic on the float32 y. SEPVAD_E_ARG (nothing
+ * launched) for a null pointer, a bad shape, a short or misaligned scratch. */
+int32_t sepvad_head_forward(const float* y, int32_t B, int32_t T, const double* hpar, void* scratch,
+                            int64_t scratch_bytes, float* masks_b, void* stream);
+
+/* The backward at y for G = d loss / d masks_b [B][514][T] with element strides g_b, g_m, g_t (>= 0: an expanded scalar
+ * has stride 0). g_y [B][256][T] (NULL: not wanted) receives d loss / d y, every element written once; gpar
+ * [SEPVAD_HEAD_NPAR] doubles (NULL: not wanted) the gradients of the folded parameters, added over time and the batch
+ * in a fixed order. The forward's intermediates are recomputed from y. No atomics: bitwise reproducible, independent of
+ * G's strides, and utterance b's g_y depends on its own rows only. SEPVAD_E_ARG (nothing launched) for a null y, G, hpar
+ * or scratch, a bad shape, a negative stride, g_y and gpar both NULL, a short or misaligned scratch. */
+int32_t sepvad_head_backward(const float* y, const float* G, int64_t g_b, int64_t g_m, int64_t g_t, int32_t B, int32_t T,
+                             const double* hpar, void* scratch, int64_t scratch_bytes, float* g_y, double* gpar,
+                             void* stream);
+
 /* ---- streaming evaluation with known targets (model/online_class_known_targets.py:85-154) --------
  * The window loop of calc_online (:101-123) for the windows of one sepvad_forward_windows chunk in a fixed number of
  * launches (csrc/stream_eval.hip): each window's PIT against its target window

@@ -770,6 +770,71 @@ int32_t sepvad_tail_backward(sepvad_handle h, const float* x, int64_t ldx, const
   HIPRET(launch_tail_grad(a, (hipStream_t)stream));
 }
 
+// The output head with a backward (model/model.py:322-325,357; csrc/head_grad.hip). Scratch: the GroupNorm
+// partials and statistics | z, shared by both directions, then the backward's dz, per-channel partials and sums, a1 and
+// a2, and the parameter partials; every array on a 256-byte boundary.
+namespace {
+static_assert(HG_NPAR == SEPVAD_HEAD_NPAR, "hpar and gpar layout (include/sepvad.h)");
+struct HeadLayout { int64_t part_stat, stat, z, dz, part_red, ub, mom, part_alpha, part_bias, part_w, total; };
+const char* head_layout(int32_t B, int32_t T, HeadLayout& L) {
+  if (B < 1 || B > 32767) return "need 1 <= B <= 32767";
+  if (T < 2 || T > (1 << 20)) return "need 2 <= T <= 2^20";
+  int64_t at = 0;
+  auto take = [&](int64_t bytes) { const int64_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+  const int64_t n = (int64_t)CH * T;
+  L.part_stat = take((int64_t)B * hg_chunks(n, HG_STAT_E) * 2 * 8); L.stat = take((int64_t)B * 2 * 8);
+  L.z = take(B * n * 4); L.dz = take(B * n * 8);
+  L.part_red = take((int64_t)B * hg_chunks(T, HG_RED_T) * CH * 2 * 8); L.ub = take((int64_t)B * CH * 2 * 8);
+  L.mom = take((int64_t)B * 2 * 8); L.part_alpha = take((int64_t)B * hg_chunks(n, HG_DY_E) * 8);
+  L.part_bias = take((int64_t)B * MOUT * 8); L.part_w = take((int64_t)B * hg_chunks(T, HG_W_T) * HG_NW * 8);
+  L.total = at;
+  return nullptr;
+}
+int32_t head_check(const std::string& e, const float* y, int32_t B, int32_t T, const double* hpar, const void* scratch,
+                   int64_t scratch_bytes, HeadLayout& L, HeadArgs& a) {
+  if (const char* why = head_layout(B, T, L)) return fail(SEPVAD_E_ARG, e + why);
+  if (!y || !hpar) return fail(SEPVAD_E_ARG, e + "null pointer");
+  if (!scratch || scratch_bytes < L.total) return fail(SEPVAD_E_ARG, e + "scratch too small (sepvad_head_scratch_bytes)");
+  if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail(SEPVAD_E_ARG, e + "scratch must be 256-byte aligned");
+  char* sc = (char*)scratch;
+  a.B = B; a.T = T; a.y = y; a.hp = hpar;
+  a.part_stat = (double*)(sc + L.part_stat); a.stat = (double*)(sc + L.stat);
+  a.z = (float*)(sc + L.z); a.dz = (double*)(sc + L.dz); a.part_red = (double*)(sc + L.part_red);
+  a.ub = (double*)(sc + L.ub); a.mom = (double*)(sc + L.mom); a.part_alpha = (double*)(sc + L.part_alpha);
+  a.part_bias = (double*)(sc + L.part_bias); a.part_w = (double*)(sc + L.part_w);
+  return SEPVAD_OK;
+}
+}  // namespace
+
+int64_t sepvad_head_scratch_bytes(int32_t B, int32_t T) {
+  HeadLayout L{};
+  if (const char* why = head_layout(B, T, L)) return fail(SEPVAD_E_ARG, std::string("sepvad_head_scratch_bytes: ") + why);
+  return L.total;
+}
+
+int32_t sepvad_head_forward(const float* y, int32_t B, int32_t T, const double* hpar, void* scratch,
+                            int64_t scratch_bytes, float* masks_b, void* stream) {
+  HeadLayout L{};
+  HeadArgs a{};
+  if (const int32_t rc = head_check("sepvad_head_forward: ", y, B, T, hpar, scratch, scratch_bytes, L, a)) return rc;
+  if (!masks_b) return fail(SEPVAD_E_ARG, "sepvad_head_forward: null pointer");
+  a.masks = masks_b;
+  HIPRET(launch_head_forward(a, (hipStream_t)stream));
+}
+
+int32_t sepvad_head_backward(const float* y, const float* G, int64_t g_b, int64_t g_m, int64_t g_t, int32_t B, int32_t T,
+                             const double* hpar, void* scratch, int64_t scratch_bytes, float* g_y, double* gpar,
+                             void* stream) {
+  HeadLayout L{};
+  HeadArgs a{};
+  if (const int32_t rc = head_check("sepvad_head_backward: ", y, B, T, hpar, scratch, scratch_bytes, L, a)) return rc;
+  if (!G) return fail(SEPVAD_E_ARG, "sepvad_head_backward: null pointer");
+  if (g_b < 0 || g_m < 0 || g_t < 0) return fail(SEPVAD_E_ARG, "sepvad_head_backward: negative stride");
+  if (!g_y && !gpar) return fail(SEPVAD_E_ARG, "sepvad_head_backward: nothing to compute");
+  a.G = G; a.g_b = g_b; a.g_m = g_m; a.g_t = g_t; a.g_y = g_y; a.gpar = gpar;
+  HIPRET(launch_head_backward(a, (hipStream_t)stream));
+}
+
 int32_t sepvad_normalize(const float* x, int64_t n, float* y, void* scratch, void* stream) {
   if (!x || !y || !scratch || n < 1) return fail(SEPVAD_E_ARG, "sepvad_normalize: bad arguments");
   static_assert(NORM_MAX_BLOCKS * 2 * sizeof(float) <= SEPVAD_NORM_SCRATCH_BYTES, "scratch size");

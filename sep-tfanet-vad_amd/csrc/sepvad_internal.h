@@ -424,6 +424,40 @@ struct TailGradArgs {
 };
 hipError_t launch_tail_grad(const TailGradArgs& a, hipStream_t s);
 
+// the output head TCN.output = PReLU -> GroupNorm(1, 256) -> conv 256 -> 514 with a backward (head_grad.hip): from the
+// trunk output y [B][256][T] to masks_b [B][514][T], and from the gradient at masks_b to the gradient at y and the
+// gradients of the head's folded parameters
+constexpr int HG_NW = MOUT * CH;              // folded weight [514][256]
+constexpr int HG_BIAS = HG_NW, HG_GAMMA = HG_BIAS + MOUT, HG_BETA = HG_GAMMA + CH, HG_ALPHA = HG_BETA + CH;
+constexpr int HG_NPAR = HG_ALPHA + 1;
+constexpr int HG_TILE = 64;       // frames per workgroup of the forward and the input-gradient products
+constexpr int HG_W_T = 128;       // frames per partial of the weight gradient (never across two utterances)
+constexpr int HG_STAT_E = 16384;  // elements of an utterance per partial of the GroupNorm sums
+constexpr int HG_RED_T = 256;     // frames per partial of the per-channel sums of dz and dz zh
+constexpr int HG_DY_E = 1024;     // elements of an utterance per workgroup of k_head_dy
+__host__ __device__ inline int hg_chunks(long long n, int per) { return (int)((n + per - 1) / per); }
+struct HeadArgs {
+  int B, T;
+  const float* y;                     // [B][256][T] trunk output
+  const double* hp;                   // [HG_NPAR] folded weight | bias | GroupNorm weight | bias | PReLU slope
+  const float* G; long long g_b, g_m, g_t;   // upstream gradient at masks_b and its element strides (backward)
+  double* part_stat;                  // scratch [B][hg_chunks(256 T, HG_STAT_E)][2] sum and sum of squares of PReLU(y)
+  double* stat;                       // scratch [B][2] mean, 1 / sqrt(var + eps)
+  float* z;                           // scratch [B][256][T] the GroupNorm output
+  double* dz;                         // scratch [B][256][T] W^T G
+  double* part_red;                   // scratch [B][hg_chunks(T, HG_RED_T)][256][2] sums of dz and of dz zh
+  double* ub;                         // scratch [B][256][2] the same per utterance
+  double* mom;                        // scratch [B][2] a1, a2
+  double* part_alpha;                 // scratch [B][hg_chunks(256 T, HG_DY_E)]
+  double* part_bias;                  // scratch [B][514]
+  double* part_w;                     // scratch [B][hg_chunks(T, HG_W_T)][514][256]
+  float* masks;                       // [B][514][T] (forward)
+  float* g_y;                         // [B][256][T] (null: parameter gradients only)
+  double* gpar;                       // [HG_NPAR] (null: the input gradient only)
+};
+hipError_t launch_head_forward(const HeadArgs& a, hipStream_t s);
+hipError_t launch_head_backward(const HeadArgs& a, hipStream_t s);
+
 // streaming evaluation with known targets (stream_eval.hip): one chunk of n windows (first window k0 of K) of B streams
 constexpr int SE_NV = 12;          // doubles per (window, segment, stream): SE_* in stream_eval.hip
 constexpr int SE_MAX_SEG = 4096;   // hop segments of one window's overlap, ceil((W - H) / H), kept in LDS by the chain

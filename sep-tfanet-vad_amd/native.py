@@ -121,6 +121,9 @@ _ABI = {
     "sepvad_tail_scratch_bytes": (i64, (i32, i32)),
     "sepvad_tail_forward": (i32, (P, P, i64, P, i32, i32, P, i64, P, P, P)),
     "sepvad_tail_backward": (i32, (P, P, i64, P, i32, i32, P, i64, i64, i64, P, i64, i64, i64, P, P, i64, P, P, P)),
+    "sepvad_head_scratch_bytes": (i64, (i32, i32)),
+    "sepvad_head_forward": (i32, (P, i32, i32, P, P, i64, P, P)),
+    "sepvad_head_backward": (i32, (P, P, i64, i64, i64, i32, i32, P, P, i64, P, P, P)),
     "sepvad_stream_eval_scratch_bytes": (i64, (i32, i32, i64, i64, i32)),
     "sepvad_stream_eval": (i32, (P, i64, i32, i32, i32, i32, i64, i64, P, i64, i32, i32, i32, i32, dbl, P, i64, P, i64,
                                  P, P, P, P, P, P, i64, P)),
