@@ -42,34 +42,44 @@ int32_t pair_metric(const char* entry, hipError_t (*launch)(const SiSdrArgs&, hi
   HIPRET(launch(sisdr_args(P, p_ld, Tg, t_ld, N, R, pidx, tidx, zero_mean, out), (hipStream_t)stream));
 }
 
-// The eval family: sepvad_eval_separation, sepvad_criterion_coef and, for what it shares, sepvad_stream_eval.
-int64_t eval_chunks(int64_t N) { return (N + EV_CHUNK - 1) / EV_CHUNK; }
-int64_t eval_scratch(int32_t B, int64_t N) {
-  return (int64_t)B * (eval_chunks(N) * EV_MOM + EV_ROWVALS) * (int64_t)sizeof(double);
-}
-// Its argument checks, in the order the entries always made them; the message starts with `entry`. B utterances of N
-// samples in rows whose smallest stride is min_ld; se_need > 0: sepvad_stream_eval, whose shapes se_layout has
-// checked and whose scratch holds se_need bytes.
-int32_t eval_check(const char* entry, int32_t B, int64_t N, int64_t min_ld, int32_t sdr_type, const void* scratch,
-                   int64_t scratch_bytes, int64_t se_need = 0) {
-  const std::string e = std::string(entry) + ": ";
-  if (!se_need) {
-    if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40)) return fail(SEPVAD_E_ARG, e + "need 1 <= B <= 65535, 1 <= N <= 2^40");
-    if (min_ld < N) return fail(SEPVAD_E_ARG, e + "row strides must be >= N");
-  }
-  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, e + "unknown sdr_type");
-  if (scratch_bytes < (se_need ? se_need : eval_scratch(B, N)))
-    return fail(SEPVAD_E_ARG, e + "scratch too small (sepvad_" + (se_need ? "stream_eval" : "eval") + "_scratch_bytes)");
-  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(SEPVAD_E_ARG, e + "scratch must be 8-byte aligned");
+// The scratch refusals of every entry that takes scratch, in their order: `e` starts the message ("<entry>: "), `need`
+// is the answer of the size query `query` for the call's shapes, `align` what the entry asks for (1: nothing).
+int32_t scratch_check(const std::string& e, const void* scratch, int64_t have, int64_t need, int align, const char* query) {
+  if (!scratch || have < need) return fail(SEPVAD_E_ARG, e + "scratch too small (" + query + ")");
+  if ((reinterpret_cast<uintptr_t>(scratch) & (uintptr_t)(align - 1)) != 0)
+    return fail(SEPVAD_E_ARG, e + "scratch must be " + std::to_string(align) + "-byte aligned");
   return SEPVAD_OK;
 }
-// The criterion fields of EvalSepArgs / CritCoefArgs; partial: the moments' partials [B][nchunk][EV_MOM]
-template <typename Args, typename Partial>
-void set_criterion(Args& a, int32_t B, int64_t N, int32_t sdr_type, int32_t zero_mean, int32_t take_log, double eps,
-                   Partial* partial) {
-  a.B = B; a.N = N; a.nchunk = (int)eval_chunks(N);
+// ... for the arrays `list` names (scratch_plan.h), which it then binds in `scratch`
+template <class L>
+int32_t scratch_bind(const std::string& e, void* scratch, int64_t have, int align, const char* query, L&& list) {
+  if (const int32_t rc = scratch_check(e, scratch, have, plan_bytes(list, align), align, query)) return rc;
+  ScratchPlan p(scratch, align);
+  list(p);
+  return SEPVAD_OK;
+}
+
+// The eval family: sepvad_eval_separation, sepvad_criterion_coef and, for what it shares, sepvad_stream_eval. Their
+// scratch is plain doubles, one array behind the other: plans with alignment 8.
+constexpr size_t EV_ALIGN = sizeof(double);
+// The criterion fields of EvalSepArgs / CritCoefArgs
+template <typename Args>
+void set_criterion(Args& a, int32_t B, int64_t N, int32_t sdr_type, int32_t zero_mean, int32_t take_log, double eps) {
+  a.B = B; a.N = N; a.nchunk = (int)((N + EV_CHUNK - 1) / EV_CHUNK);
   a.sdr_type = sdr_type; a.zero_mean = zero_mean != 0; a.take_log = take_log != 0; a.eps = eps;
-  a.partial = partial;
+}
+// The evaluation's scratch, each array once (a.B and a.nchunk are set)
+void eval_scratch(EvalSepArgs& a, ScratchPlan& p) {
+  p.take(a.partial, (size_t)a.B * a.nchunk * EV_MOM); p.take(a.rowvals, (size_t)a.B * EV_ROWVALS);
+}
+// The checks sepvad_eval_separation and sepvad_criterion_coef share, in their order (min_ld: the smallest row stride)
+int32_t eval_check(const char* entry, int32_t B, int64_t N, int64_t min_ld, int32_t sdr_type, const void* scratch,
+                   int64_t scratch_bytes) {
+  const std::string e = std::string(entry) + ": ";
+  if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40)) return fail(SEPVAD_E_ARG, e + "need 1 <= B <= 65535, 1 <= N <= 2^40");
+  if (min_ld < N) return fail(SEPVAD_E_ARG, e + "row strides must be >= N");
+  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, e + "unknown sdr_type");
+  return scratch_check(e, scratch, scratch_bytes, sepvad_eval_scratch_bytes(B, N), EV_ALIGN, "sepvad_eval_scratch_bytes");
 }
 }  // namespace
 
@@ -351,8 +361,8 @@ int32_t sepvad_pit_l1_rows(const float* est, int64_t est_ld, const float* ref, i
   if (!est || !ref || !scratch) return fail(SEPVAD_E_ARG, "sepvad_pit_l1_rows: null pointer");
   if (B < 1 || B > 65535 || L < 1 || est_ld < L || ref_ld < L)
     return fail(SEPVAD_E_ARG, "sepvad_pit_l1_rows: need 1 <= B <= 65535, L >= 1 and row strides >= L");
-  if (scratch_bytes < (int64_t)B * pit_row_blocks(L) * 4 * (int64_t)sizeof(double))
-    return fail(SEPVAD_E_ARG, "sepvad_pit_l1_rows: scratch too small (sepvad_pit_l1_rows_scratch_bytes)");
+  if (const int32_t rc = scratch_check("sepvad_pit_l1_rows: ", scratch, scratch_bytes, sepvad_pit_l1_rows_scratch_bytes(B, L), 1,
+                                       "sepvad_pit_l1_rows_scratch_bytes")) return rc;
   HIPRET(launch_pit_l1_rows(pit_args(est, est_ld, ref, ref_ld, B, L, pit_row_blocks(L), scratch, perm_out, loss_out, pw_out),
                             (hipStream_t)stream));
 }
@@ -451,67 +461,68 @@ static bool stoi_shape_ok(int32_t R, int64_t N, int up, int down) {
   return nF >= 1 && (long long)R * 2 * STOI_BANDS * nF < (1LL << 40);
 }
 
-int64_t sepvad_stoi_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig) {
+static_assert(STOI_MODE_CLASSIC == SEPVAD_STOI_CLASSIC && STOI_MODE_EXTENDED == SEPVAD_STOI_EXTENDED, "sepvad.h");
+static bool stoi_modes_ok(int32_t modes) { return modes >= 1 && modes <= (SEPVAD_STOI_CLASSIC | SEPVAD_STOI_EXTENDED); }
+
+// The shape refusals of the STOI entries and size queries (`e`: whose), from the host design alone; a's shapes
+static int32_t stoi_shape(const std::string& e, int32_t R, int64_t N, int32_t fs_sig, int32_t modes, StoiArgs& a) {
   StoiDesign d;
-  if (!stoi_design(fs_sig, d)) return fail(SEPVAD_E_ARG, "sepvad_stoi_scratch_bytes: fs_sig must be 8000, 10000 or 16000");
+  if (!stoi_design(fs_sig, d)) return fail(SEPVAD_E_ARG, e + "fs_sig must be 8000, 10000 or 16000");
+  if (!stoi_modes_ok(modes)) return fail(SEPVAD_E_ARG, e + "modes must be 1, 2 or 3");
   if (!stoi_shape_ok(R, N, d.up, d.down))
-    return fail(SEPVAD_E_ARG, "sepvad_stoi_scratch_bytes: need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
-  return stoi_scratch_layout(R, N, d.up, d.down, nullptr, nullptr);
+    return fail(SEPVAD_E_ARG, e + "need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
+  a.N = N; a.R = R; a.up = d.up; a.down = d.down;
+  return SEPVAD_OK;
+}
+
+static int64_t stoi_bytes(const std::string& e, int32_t R, int64_t N, int32_t fs_sig, int32_t modes) {
+  StoiArgs a{};
+  if (const int32_t rc = stoi_shape(e, R, N, fs_sig, modes, a)) return rc;
+  return plan_bytes([&](ScratchPlan& p) { stoi_scratch(a, modes, p); });
+}
+int64_t sepvad_stoi_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig) {
+  return stoi_bytes("sepvad_stoi_scratch_bytes: ", R, N, fs_sig, SEPVAD_STOI_CLASSIC);
+}
+int64_t sepvad_stoi_ex_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig, int32_t modes) {
+  return stoi_bytes("sepvad_stoi_ex_scratch_bytes: ", R, N, fs_sig, modes);
+}
+
+// sepvad_stoi_ex, and sepvad_stoi as its classic mode; `entry` names the caller in the messages. Every refusal comes
+// before the first HIP call (stoi_tables uploads the design): the host design gives up / down.
+static int32_t stoi_entry(const std::string& entry, const float* X, int64_t x_ld, const float* Y, int64_t y_ld, int64_t N,
+                          int32_t R, const int32_t* xidx, const int32_t* yidx, int32_t fs_sig, void* scratch,
+                          int64_t scratch_bytes, int32_t modes, double* out_stoi, double* out_estoi, int32_t* frames,
+                          void* stream) {
+  const std::string e = entry + ": ";
+  if (!X || !Y || !scratch || N < 1 || x_ld < N || y_ld < N) return fail(SEPVAD_E_ARG, e + "bad arguments");
+  if (!stoi_modes_ok(modes)) return fail(SEPVAD_E_ARG, e + "modes must be 1, 2 or 3");
+  if (((modes & SEPVAD_STOI_CLASSIC) && !out_stoi) || ((modes & SEPVAD_STOI_EXTENDED) && !out_estoi))
+    return fail(SEPVAD_E_ARG, e + "a requested mode has no output pointer");
+  StoiArgs a{};
+  if (const int32_t rc = stoi_shape(e, R, N, fs_sig, modes, a)) return rc;
+  if (const int32_t rc = scratch_bind(e, scratch, scratch_bytes, 256, (entry + "_scratch_bytes").c_str(),
+                                      [&](ScratchPlan& p) { stoi_scratch(a, modes, p); })) return rc;
+  HIPCHK(stoi_tables(fs_sig, a));
+  a.X = X; a.x_ld = x_ld; a.Y = Y; a.y_ld = y_ld; a.xidx = xidx; a.yidx = yidx;
+  a.out = (modes & SEPVAD_STOI_CLASSIC) ? out_stoi : nullptr;
+  a.out_ex = (modes & SEPVAD_STOI_EXTENDED) ? out_estoi : nullptr;
+  a.frames = frames;
+  HIPRET(launch_stoi_ex(a, modes, (hipStream_t)stream));
 }
 
 int32_t sepvad_stoi(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, int64_t N, int32_t R,
                     const int32_t* xidx, const int32_t* yidx, int32_t fs_sig, void* scratch, int64_t scratch_bytes,
                     double* out, int32_t* frames, void* stream) {
-  if (!X || !Y || !out || !scratch || N < 1 || x_ld < N || y_ld < N) return fail(SEPVAD_E_ARG, "sepvad_stoi: bad arguments");
-  if (!stoi_rate_supported(fs_sig)) return fail(SEPVAD_E_ARG, "sepvad_stoi: fs_sig must be 8000, 10000 or 16000");
-  StoiArgs a{};
-  HIPCHK(stoi_tables(fs_sig, a));
-  if (!stoi_shape_ok(R, N, a.up, a.down))
-    return fail(SEPVAD_E_ARG, "sepvad_stoi: need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
-  if (scratch_bytes < stoi_scratch_layout(R, N, a.up, a.down, &a, (char*)scratch))
-    return fail(SEPVAD_E_ARG, "sepvad_stoi: scratch too small (sepvad_stoi_scratch_bytes)");
-  if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail(SEPVAD_E_ARG, "sepvad_stoi: scratch must be 256-byte aligned");
-  a.X = X; a.x_ld = x_ld; a.Y = Y; a.y_ld = y_ld; a.xidx = xidx; a.yidx = yidx; a.N = N; a.R = R;
-  a.out = out; a.frames = frames;
-  HIPRET(launch_stoi(a, (hipStream_t)stream));
-}
-
-static_assert(STOI_MODE_CLASSIC == SEPVAD_STOI_CLASSIC && STOI_MODE_EXTENDED == SEPVAD_STOI_EXTENDED, "sepvad.h");
-static bool stoi_modes_ok(int32_t modes) { return modes >= 1 && modes <= (SEPVAD_STOI_CLASSIC | SEPVAD_STOI_EXTENDED); }
-
-int64_t sepvad_stoi_ex_scratch_bytes(int32_t R, int64_t N, int32_t fs_sig, int32_t modes) {
-  StoiDesign d;
-  if (!stoi_design(fs_sig, d))
-    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex_scratch_bytes: fs_sig must be 8000, 10000 or 16000");
-  if (!stoi_modes_ok(modes)) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex_scratch_bytes: modes must be 1, 2 or 3");
-  if (!stoi_shape_ok(R, N, d.up, d.down))
-    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex_scratch_bytes: need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
-  return stoi_ex_scratch_layout(R, N, d.up, d.down, modes, nullptr, nullptr);
+  if (!out) return fail(SEPVAD_E_ARG, "sepvad_stoi: bad arguments");  // (its word for a missing output)
+  return stoi_entry("sepvad_stoi", X, x_ld, Y, y_ld, N, R, xidx, yidx, fs_sig, scratch, scratch_bytes, SEPVAD_STOI_CLASSIC,
+                    out, nullptr, frames, stream);
 }
 
 int32_t sepvad_stoi_ex(const float* X, int64_t x_ld, const float* Y, int64_t y_ld, int64_t N, int32_t R,
                        const int32_t* xidx, const int32_t* yidx, int32_t fs_sig, void* scratch, int64_t scratch_bytes,
                        int32_t modes, double* out_stoi, double* out_estoi, int32_t* frames, void* stream) {
-  if (!X || !Y || !scratch || N < 1 || x_ld < N || y_ld < N) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: bad arguments");
-  if (!stoi_modes_ok(modes)) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: modes must be 1, 2 or 3");
-  if (((modes & SEPVAD_STOI_CLASSIC) && !out_stoi) || ((modes & SEPVAD_STOI_EXTENDED) && !out_estoi))
-    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: a requested mode has no output pointer");
-  // every refusal comes before the first HIP call (stoi_tables uploads the design): the host design gives up / down
-  StoiDesign d;
-  if (!stoi_design(fs_sig, d)) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: fs_sig must be 8000, 10000 or 16000");
-  if (!stoi_shape_ok(R, N, d.up, d.down))
-    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: need 1 <= R <= 65535 and more than 256 samples at 10 kHz");
-  if (scratch_bytes < stoi_ex_scratch_layout(R, N, d.up, d.down, modes, nullptr, nullptr))
-    return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: scratch too small (sepvad_stoi_ex_scratch_bytes)");
-  if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail(SEPVAD_E_ARG, "sepvad_stoi_ex: scratch must be 256-byte aligned");
-  StoiArgs a{};
-  HIPCHK(stoi_tables(fs_sig, a));
-  stoi_ex_scratch_layout(R, N, a.up, a.down, modes, &a, (char*)scratch);
-  a.X = X; a.x_ld = x_ld; a.Y = Y; a.y_ld = y_ld; a.xidx = xidx; a.yidx = yidx; a.N = N; a.R = R;
-  a.out = (modes & SEPVAD_STOI_CLASSIC) ? out_stoi : nullptr;
-  a.out_ex = (modes & SEPVAD_STOI_EXTENDED) ? out_estoi : nullptr;
-  a.frames = frames;
-  HIPRET(launch_stoi_ex(a, modes, (hipStream_t)stream));
+  return stoi_entry("sepvad_stoi_ex", X, x_ld, Y, y_ld, N, R, xidx, yidx, fs_sig, scratch, scratch_bytes, modes, out_stoi,
+                    out_estoi, frames, stream);
 }
 
 int32_t sepvad_vad_accuracy(float* preds, const float* targets, int32_t B, int32_t S, int32_t T, int32_t in_place,
@@ -526,7 +537,9 @@ int32_t sepvad_vad_accuracy(float* preds, const float* targets, int32_t B, int32
 int64_t sepvad_eval_scratch_bytes(int32_t B, int64_t N) {
   if (B < 1 || B > 65535 || N < 1 || N > (1LL << 40))
     return fail(SEPVAD_E_ARG, "sepvad_eval_scratch_bytes: need 1 <= B <= 65535, 1 <= N <= 2^40");
-  return eval_scratch(B, N);
+  EvalSepArgs a{};
+  set_criterion(a, B, N, 0, 0, 0, 0.0);
+  return plan_bytes([&](ScratchPlan& p) { eval_scratch(a, p); }, EV_ALIGN);
 }
 
 // PITLossWrapper(PairwiseNegSDR(...), "pw_mtx") (model/sdr.py:48-86, model/pit_wrapper.py:100-145,287-312) and the
@@ -542,43 +555,45 @@ int32_t sepvad_eval_separation(const float* est, int64_t est_ld, const float* tg
     return rc;
   EvalSepArgs a{};
   a.est = est; a.est_ld = est_ld; a.tgt = tgt; a.tgt_ld = tgt_ld; a.mix = mix; a.mix_ld = mix_ld;
-  set_criterion(a, B, N, sdr_type, zero_mean, take_log, eps, (double*)scratch);
-  a.rowvals = a.partial + (int64_t)B * a.nchunk * EV_MOM;
+  set_criterion(a, B, N, sdr_type, zero_mean, take_log, eps);
+  ScratchPlan p(scratch, EV_ALIGN);
+  eval_scratch(a, p);
   a.pw = pw; a.min_loss = min_loss; a.perm = (long long*)perm; a.sheet = sheet; a.means = means;
   HIPRET(launch_eval_separation(a, (hipStream_t)stream));
 }
 
 // calc_online's window loop with known targets (model/online_class_known_targets.py:101-123): csrc/stream_eval.hip.
-// Scratch (doubles): segment sums [n][S][B][SE_NV] | their batch sums [n][S][4] | launch_pit_l1's scratch | the target
-// moments' partials [n B][nchunk][EV_MOM] | eval.hip's row values [n B][EV_ROWVALS]
 namespace {
-struct SeLayout { int64_t seg, bsum, pit0, partial, rowvals, total; int S, nchunk; };
-const char* se_layout(int32_t B, int32_t n, int64_t W, int64_t H, int32_t mode, SeLayout& L) {
-  if (B < 1 || B > 65535 || n < 1) return "need 1 <= B <= 65535 and n >= 1";
-  if (H < 1 || H > W || W > INT32_MAX) return "need 1 <= H <= W < 2^31";
-  if (mode < SEPVAD_SE_NONE || mode > SEPVAD_SE_SISDR) return "unknown mode";
-  const bool sim = mode != SEPVAD_SE_NONE;
-  if (sim && 2 * H > W) return "a similarity mode needs 2 H <= W (the reference's slices stop matching beyond)";
-  L.S = sim ? se_segments(W, H) : 0;
-  if (L.S > SE_MAX_SEG) return "a similarity mode takes at most 4096 hops per window";
-  L.nchunk = (int)((W + EV_CHUNK - 1) / EV_CHUNK);
-  const int64_t nu = (int64_t)n * B;
-  if (nu * ((int64_t)L.S + L.nchunk) > INT32_MAX) return "the chunk exceeds 2^31 - 1 workgroups (fewer windows per call)";
-  L.seg = 0;
-  L.bsum = L.seg + nu * L.S * SE_NV;
-  L.pit0 = L.bsum + (mode == SEPVAD_SE_L1 ? (int64_t)n * L.S * 4 : 0);
-  L.partial = L.pit0 + (mode == SEPVAD_SE_L1 ? SEPVAD_PIT_SCRATCH_BYTES / (int64_t)sizeof(double) : 0);
-  L.rowvals = L.partial + nu * L.nchunk * EV_MOM;
-  L.total = (L.rowvals + nu * EV_ROWVALS) * (int64_t)sizeof(double);
+// The shape refusals of sepvad_stream_eval and its size query (null: none); fills a's shapes, S, ev.B and ev.nchunk
+const char* se_shape(StreamEvalArgs& a, int32_t B, int32_t n, int64_t W, int64_t H, int32_t mode) {
+  a.B = B; a.n = n; a.W = W; a.H = H; a.mode = mode;
+  if (a.B < 1 || a.B > 65535 || a.n < 1) return "need 1 <= B <= 65535 and n >= 1";
+  if (a.H < 1 || a.H > a.W || a.W > INT32_MAX) return "need 1 <= H <= W < 2^31";
+  if (a.mode < SEPVAD_SE_NONE || a.mode > SEPVAD_SE_SISDR) return "unknown mode";
+  const bool sim = a.mode != SEPVAD_SE_NONE;
+  if (sim && 2 * a.H > a.W) return "a similarity mode needs 2 H <= W (the reference's slices stop matching beyond)";
+  a.S = sim ? se_segments(a.W, a.H) : 0;
+  if (a.S > SE_MAX_SEG) return "a similarity mode takes at most 4096 hops per window";
+  a.ev.nchunk = (int)((a.W + EV_CHUNK - 1) / EV_CHUNK);
+  const int64_t nu = (int64_t)a.n * a.B;
+  if (nu * ((int64_t)a.S + a.ev.nchunk) > INT32_MAX) return "the chunk exceeds 2^31 - 1 workgroups (fewer windows per call)";
+  a.ev.B = (int)nu;
   return nullptr;
+}
+// Its scratch, each array once: with SEPVAD_SE_L1 also the batch sums and launch_pit_l1's scratch; last the evaluation's
+void se_scratch(StreamEvalArgs& a, double*& pit0, ScratchPlan& p) {
+  const bool l1 = a.mode == SEPVAD_SE_L1;
+  p.take(a.seg, (size_t)a.ev.B * a.S * SE_NV); p.take(a.bsum, l1 ? (size_t)a.n * a.S * 4 : 0);
+  p.take(pit0, l1 ? SEPVAD_PIT_SCRATCH_BYTES / sizeof(double) : 0);
+  eval_scratch(a.ev, p);
 }
 }  // namespace
 
 int64_t sepvad_stream_eval_scratch_bytes(int32_t B, int32_t n, int64_t W, int64_t H, int32_t mode) {
-  SeLayout L{};
-  if (const char* why = se_layout(B, n, W, H, mode, L))
-    return fail(SEPVAD_E_ARG, std::string("sepvad_stream_eval_scratch_bytes: ") + why);
-  return L.total;
+  StreamEvalArgs a{};
+  if (const char* why = se_shape(a, B, n, W, H, mode)) return fail(SEPVAD_E_ARG, std::string("sepvad_stream_eval_scratch_bytes: ") + why);
+  double* pit0 = nullptr;
+  return plan_bytes([&](ScratchPlan& p) { se_scratch(a, pit0, p); }, EV_ALIGN);
 }
 
 int32_t sepvad_stream_eval(const float* sep, int64_t sep_ld, int32_t n, int32_t k0, int32_t K, int32_t B, int64_t W,
@@ -586,27 +601,26 @@ int32_t sepvad_stream_eval(const float* sep, int64_t sep_ld, int32_t n, int32_t 
                            int32_t zero_mean, int32_t take_log, double eps, float* raw, int64_t raw_ld, float* online,
                            int64_t online_ld, int64_t* perm, int64_t* perm_tgt, float* pw_tgt, float* loss_tgt,
                            float* pw_sim, void* scratch, int64_t scratch_bytes, void* stream) {
-  SeLayout L{};
-  if (const char* why = se_layout(B, n, W, H, mode, L)) return fail(SEPVAD_E_ARG, std::string("sepvad_stream_eval: ") + why);
-  if (!sep || !tgt || !raw || !online || !perm || !pw_tgt || !loss_tgt || !scratch || (mode != SEPVAD_SE_NONE && !perm_tgt))
-    return fail(SEPVAD_E_ARG, "sepvad_stream_eval: null pointer");
-  if (k0 < 0 || K < 1 || (int64_t)k0 + n > K) return fail(SEPVAD_E_ARG, "sepvad_stream_eval: need 0 <= k0 and k0 + n <= K");
-  if (sep_ld < W || tgt_ld < (int64_t)(K - 1) * H + W || raw_ld < (int64_t)K * H || online_ld < (int64_t)K * H)
-    return fail(SEPVAD_E_ARG, "sepvad_stream_eval: row strides must cover W (sep), (K - 1) H + W (tgt) and K H (raw, online)");
-  if (const int32_t rc = eval_check("sepvad_stream_eval", n * B, W, W, sdr_type, scratch, scratch_bytes, L.total)) return rc;
+  const std::string er = "sepvad_stream_eval: ";
   StreamEvalArgs a{};
-  a.B = B; a.n = n; a.k0 = k0; a.K = K; a.mode = mode; a.W = W; a.H = H; a.S = L.S;
-  a.sep = sep; a.sep_ld = sep_ld; a.raw = raw; a.raw_ld = raw_ld; a.online = online; a.on_ld = online_ld;
+  if (const char* why = se_shape(a, B, n, W, H, mode)) return fail(SEPVAD_E_ARG, er + why);
+  if (!sep || !tgt || !raw || !online || !perm || !pw_tgt || !loss_tgt || !scratch || (mode != SEPVAD_SE_NONE && !perm_tgt))
+    return fail(SEPVAD_E_ARG, er + "null pointer");
+  if (k0 < 0 || K < 1 || (int64_t)k0 + n > K) return fail(SEPVAD_E_ARG, er + "need 0 <= k0 and k0 + n <= K");
+  if (sep_ld < W || tgt_ld < (int64_t)(K - 1) * H + W || raw_ld < (int64_t)K * H || online_ld < (int64_t)K * H)
+    return fail(SEPVAD_E_ARG, er + "row strides must cover W (sep), (K - 1) H + W (tgt) and K H (raw, online)");
+  if (sdr_type < SEPVAD_SDR_SISDR || sdr_type > SEPVAD_SDR_SNR) return fail(SEPVAD_E_ARG, er + "unknown sdr_type");
+  double* pit0 = nullptr;
+  if (const int32_t rc = scratch_bind(er, scratch, scratch_bytes, EV_ALIGN, "sepvad_stream_eval_scratch_bytes",
+                                      [&](ScratchPlan& p) { se_scratch(a, pit0, p); })) return rc;
+  a.k0 = k0; a.K = K; a.sep = sep; a.sep_ld = sep_ld; a.raw = raw; a.raw_ld = raw_ld; a.online = online; a.on_ld = online_ld;
   a.perm = (long long*)perm; a.pw_sim = pw_sim;
-  double* sc = (double*)scratch;
-  a.seg = sc + L.seg; a.bsum = sc + L.bsum;
-  if (mode == SEPVAD_SE_L1 && k0 == 0)  // window 0's seed comparison: its second-last hop against its own last hop
-    a.pit0 = pit_args(sep + (W - 2 * H), sep_ld, raw, raw_ld, B, H, pit_batch_blocks(B, H), sc + L.pit0, perm, nullptr, pw_sim);
-  const int64_t w0 = (int64_t)k0 * B;  // the per-window outputs of this chunk start at window k0
   EvalSepArgs& e = a.ev;
+  set_criterion(e, n * B, W, sdr_type, zero_mean, take_log, eps);  // (B and nchunk as se_shape left them)
+  if (mode == SEPVAD_SE_L1 && k0 == 0)  // window 0's seed comparison: its second-last hop against its own last hop
+    a.pit0 = pit_args(sep + (W - 2 * H), sep_ld, raw, raw_ld, B, H, pit_batch_blocks(B, H), pit0, perm, nullptr, pw_sim);
+  const int64_t w0 = (int64_t)k0 * B;  // the per-window outputs of this chunk start at window k0
   e.est = sep; e.est_ld = sep_ld; e.tgt = tgt + (int64_t)k0 * H; e.tgt_ld = tgt_ld;
-  set_criterion(e, n * B, W, sdr_type, zero_mean, take_log, eps, sc + L.partial);  // nchunk == L.nchunk
-  e.rowvals = sc + L.rowvals;
   e.pw = pw_tgt + w0 * 4; e.min_loss = loss_tgt + w0;
   e.perm = (long long*)(mode == SEPVAD_SE_NONE ? perm : perm_tgt) + w0 * 2;
   HIPRET(launch_stream_eval(a, (hipStream_t)stream));
@@ -640,7 +654,8 @@ int32_t sepvad_criterion_coef(const float* est, int64_t est_ld, const float* tgt
     return rc;
   CritCoefArgs a{};
   a.est = est; a.est_ld = est_ld; a.tgt = tgt; a.tgt_ld = tgt_ld;
-  set_criterion(a, B, N, sdr_type, zero_mean, take_log, eps, (const double*)scratch);
+  set_criterion(a, B, N, sdr_type, zero_mean, take_log, eps);
+  a.partial = (const double*)scratch;  // the first array of eval_scratch, as sepvad_eval_separation left it
   a.perm = (const long long*)perm; a.coef = coef;
   HIPRET(launch_crit_coef(a, (hipStream_t)stream));
 }
@@ -670,81 +685,60 @@ int32_t sepvad_criterion_backward(int32_t B, const float* est, int64_t est_ld, c
   HIPRET(launch_crit_grad(a, (hipStream_t)stream));
 }
 
-// The tail with a backward (model/model.py:421-461; csrc/tail_grad.hip). Scratch: the forward's
-// frame-major buffers (X | dB spectrum | TCN input | TCN.LN records | conv1_1 output | BN_1 records), overlaid by the
-// backward's (conv1_1 output in double | g_z | g_y in double and in float32 | the rows' partials), every array on a 256-byte boundary.
+// The tail with a backward (model/model.py:421-461; csrc/tail_grad.hip).
 namespace {
 static_assert(TG_NPAR == SEPVAD_TAIL_NPAR, "gpar layout (include/sepvad.h)");
-struct TailLayout { int64_t X, specdb, S0, rec_gate, vy, rec_vad, feat, gz, gyd, gy, part_small, part_w1, total; int T, Tp; };
-const char* tail_layout(int32_t B, int32_t N, TailLayout& L) {
+const char* tail_shape(int32_t B, int32_t N) {
   if (B < 1 || B > 32767) return "need 1 <= B <= 32767";
-  if (N <= HOP || N >= (1 << 29)) return "need 256 < N < 2^29 (reflect padding of the STFT)";
-  L.T = 1 + N / HOP; L.Tp = round_up(L.T, TILE);
-  int64_t at = 0;
-  auto take = [&](int64_t bytes) { const int64_t o = at; at += (bytes + 255) / 256 * 256; return o; };
-  const int64_t rows = (int64_t)B * L.Tp;
-  L.X = take(rows * NBIN * 8); L.specdb = take(rows * SPEC_LD * 4); L.S0 = take(rows * CH * 4);
-  L.rec_gate = take(rows / GATE_ROWS * 2 * 8); L.vy = take(rows * 8 * 4); L.rec_vad = take(rows / VAD_ROWS * 4 * 8);
-  const int64_t fwd = at, bst = (int64_t)B * 2 * L.T;
-  at = 0;
-  L.feat = take(bst * 4 * 8); L.gz = take(bst * 8); L.gyd = take(bst * 4 * 8); L.gy = take(bst * 4 * 4);
-  L.part_small = take((int64_t)B * 2 * TG_NSMALL * 8); L.part_w1 = take((int64_t)B * 2 * tg_w1_chunks(L.T) * TG_NW1 * 8);
-  L.total = std::max(fwd, at);
-  return nullptr;
+  return N <= HOP || N >= (1 << 29) ? "need 256 < N < 2^29 (reflect padding of the STFT)" : nullptr;
 }
-int32_t tail_check(const std::string& e, sepvad_handle h, int32_t B, int32_t N, int64_t ldx, const void* scratch,
-                   int64_t scratch_bytes, TailLayout& L) {
+// Its scratch, each array once: the forward's frame-major buffers as the workspace has them (handle.h ws_each; the
+// record arrays without its slack), then over the same bytes the backward's arrays (sepvad_internal.h TailGradArgs)
+void tail_scratch(Workspace& w, TailGradArgs& g, int32_t B, int32_t N, ScratchPlan& p) {
+  const int T = 1 + N / HOP;
+  const size_t rows = (size_t)B * round_up(T, TILE), bst = (size_t)B * 2 * T;
+  p.take(w.X, rows * NBIN); p.take(w.specdb, rows * SPEC_LD); p.take(w.S0, rows * CH);
+  p.take(w.rec_gate, rows / GATE_ROWS * 2); p.take(w.vy, rows * 2 * 4); p.take(w.rec_vad, rows / VAD_ROWS * 2 * 2);
+  p.rewind();
+  p.take(g.feat, bst * 4); p.take(g.gz, bst); p.take(g.gyd, bst * 4); p.take(g.gy, bst * 4);
+  p.take(g.part_small, (size_t)B * 2 * TG_NSMALL); p.take(g.part_w1, (size_t)B * 2 * tg_w1_chunks(T) * TG_NW1);
+}
+// The refusals both directions share, then the arrays of w and g in the caller's scratch
+int32_t tail_check(const std::string& e, sepvad_handle h, int32_t B, int32_t N, int64_t ldx, void* scratch,
+                   int64_t scratch_bytes, Workspace& w, TailGradArgs& g) {
   if (!h) return fail(SEPVAD_E_ARG, e + "null handle");
-  if (const char* why = tail_layout(B, N, L)) return fail(SEPVAD_E_ARG, e + why);
+  if (const char* why = tail_shape(B, N)) return fail(SEPVAD_E_ARG, e + why);
   if (ldx < N || ldx > INT32_MAX) return fail(SEPVAD_E_ARG, e + "row stride must be >= N");
   if (h->cfg.final_vad && h->cfg.final_vad_masked_speakers)
     return fail(SEPVAD_E_ARG, e + "final_vad_masked_speakers has no backward");
-  if (!scratch || scratch_bytes < L.total) return fail(SEPVAD_E_ARG, e + "scratch too small (sepvad_tail_scratch_bytes)");
-  if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail(SEPVAD_E_ARG, e + "scratch must be 256-byte aligned");
-  return SEPVAD_OK;
+  return scratch_bind(e, scratch, scratch_bytes, 256, "sepvad_tail_scratch_bytes",
+                      [&](ScratchPlan& p) { tail_scratch(w, g, B, N, p); });
 }
 }  // namespace
 
 int64_t sepvad_tail_scratch_bytes(int32_t B, int32_t N) {
-  TailLayout L{};
-  if (const char* why = tail_layout(B, N, L)) return fail(SEPVAD_E_ARG, std::string("sepvad_tail_scratch_bytes: ") + why);
-  return L.total;
+  if (const char* why = tail_shape(B, N)) return fail(SEPVAD_E_ARG, std::string("sepvad_tail_scratch_bytes: ") + why);
+  Workspace w{}; TailGradArgs g{};
+  return plan_bytes([&](ScratchPlan& p) { tail_scratch(w, g, B, N, p); });
 }
 
 int32_t sepvad_tail_forward(sepvad_handle h, const float* x, int64_t ldx, const float* masks_fm, int32_t B, int32_t N,
                             void* scratch, int64_t scratch_bytes, float* sep, float* vad, void* stream) {
-  TailLayout L{};
-  if (const int32_t rc = tail_check("sepvad_tail_forward: ", h, B, N, ldx, scratch, scratch_bytes, L)) return rc;
-  const bool has_vad = h->cfg.final_vad != 0;
-  if (!x || !masks_fm || !sep || (has_vad && !vad)) return fail(SEPVAD_E_ARG, "sepvad_tail_forward: null pointer");
+  Workspace w{}; TailGradArgs unused{};
+  if (const int32_t rc = tail_check("sepvad_tail_forward: ", h, B, N, ldx, scratch, scratch_bytes, w, unused)) return rc;
+  if (!x || !masks_fm || !sep || (h->cfg.final_vad && !vad)) return fail(SEPVAD_E_ARG, "sepvad_tail_forward: null pointer");
   DeviceGuard dg(h->device);
-  const hipStream_t s = (hipStream_t)stream;
-  char* sc = (char*)scratch;
-  Workspace w{};
-  w.X = (float2*)(sc + L.X); w.specdb = (float*)(sc + L.specdb); w.S0 = (float*)(sc + L.S0);
-  w.rec_gate = (double*)(sc + L.rec_gate); w.vy = (float*)(sc + L.vy); w.rec_vad = (double*)(sc + L.rec_vad);
-  HIPCHK(launch_stft_gate(stft_gate_args(h, w, x, (int)ldx, B, N), s));  // the front end, for X
-  IstftArgs is = istft_pair_args(h, w.X, masks_fm, B, N);
-  if (has_vad) {  // the multi-kernel schedule's VAD stage and tail (forward.hip vad_stage, back_end)
-    Vad1Args v{};
-    v.B = B; v.T = L.T; v.Tp = L.Tp; v.masks = masks_fm; v.X = w.X;
-    v.w1 = h->P(h->v_w1); v.b1 = h->P(h->v_b1); v.alpha = h->v_a; v.vy = w.vy; v.out_rec = w.rec_vad;
-    HIPCHK(launch_vad1(v, s));
-    is.has_vad = 1; is.thr = 0.5f;
-    is.vy = w.vy; is.w2 = h->P(h->v_w2); is.b2 = h->v_b2;
-    is.vgn = GnSrc{w.rec_vad, L.Tp / VAD_ROWS, 2, 0, h->P(h->v_g), h->P(h->v_b), 1e-8f};
-    is.vad_out = vad;
-  }
-  is.y = sep;
-  HIPRET(launch_istft_pair(is, s));
+  w.masks = const_cast<float*>(masks_fm);  // (read only by the stages that run)
+  return tail_stages(h, w, x, (int)ldx, B, N, sep, vad, (hipStream_t)stream);
 }
 
 int32_t sepvad_tail_backward(sepvad_handle h, const float* x, int64_t ldx, const float* masks_b, int32_t B, int32_t N,
                              const float* g_sep, int64_t gs_b, int64_t gs_s, int64_t gs_n, const float* g_vad,
                              int64_t gv_b, int64_t gv_s, int64_t gv_t, const double* vadw, void* scratch,
                              int64_t scratch_bytes, float* g_masks, double* gpar, void* stream) {
-  TailLayout L{};
-  if (const int32_t rc = tail_check("sepvad_tail_backward: ", h, B, N, ldx, scratch, scratch_bytes, L)) return rc;
+  Workspace unused{}; TailGradArgs a{}, no_vad{};  // (the scratch arrays are bound only with a VAD gradient)
+  if (const int32_t rc = tail_check("sepvad_tail_backward: ", h, B, N, ldx, scratch, scratch_bytes, unused, g_vad ? a : no_vad))
+    return rc;
   if (!x || !masks_b) return fail(SEPVAD_E_ARG, "sepvad_tail_backward: null pointer");
   if (!g_sep && !g_vad) return fail(SEPVAD_E_ARG, "sepvad_tail_backward: neither upstream gradient");
   if (!g_masks && !(g_vad && gpar)) return fail(SEPVAD_E_ARG, "sepvad_tail_backward: nothing to compute");
@@ -753,70 +747,43 @@ int32_t sepvad_tail_backward(sepvad_handle h, const float* x, int64_t ldx, const
   if (gs_b < 0 || gs_s < 0 || gs_n < 0 || gv_b < 0 || gv_s < 0 || gv_t < 0)
     return fail(SEPVAD_E_ARG, "sepvad_tail_backward: negative stride");
   DeviceGuard dg(h->device);
-  char* sc = (char*)scratch;
-  TailGradArgs a{};
-  a.B = B; a.N = N; a.T = L.T; a.x = x; a.ldx = ldx; a.masks = masks_b;
+  a.B = B; a.N = N; a.T = 1 + N / HOP; a.x = x; a.ldx = ldx; a.masks = masks_b;
   a.g_sep = g_sep; a.gs_b = gs_b; a.gs_s = gs_s; a.gs_n = gs_n;
   a.g_vad = g_vad; a.gv_b = gv_b; a.gv_s = gv_s; a.gv_t = gv_t;
   a.win_x = h->P(h->win_out); a.win_inv = h->P(h->win_inv); a.tw = (const float2*)h->P(h->tw);
-  if (g_vad) {
-    a.vw = vadw; a.eps = 1e-8f;
-    a.feat = (double*)(sc + L.feat); a.gz = (double*)(sc + L.gz);
-    a.gyd = (double*)(sc + L.gyd); a.gy = (float*)(sc + L.gy);
-    a.part_small = (double*)(sc + L.part_small); a.part_w1 = (double*)(sc + L.part_w1);
-    a.gpar = gpar;
-  }
+  if (g_vad) { a.vw = vadw; a.eps = 1e-8f; a.gpar = gpar; }
   a.g_masks = g_masks;
   HIPRET(launch_tail_grad(a, (hipStream_t)stream));
 }
 
-// The output head with a backward (model/model.py:322-325,357; csrc/head_grad.hip). Scratch: the GroupNorm
-// partials and statistics | z, shared by both directions, then the backward's dz, per-channel partials and sums, a1 and
-// a2, and the parameter partials; every array on a 256-byte boundary.
+// The output head with a backward (model/model.py:322-325,357; csrc/head_grad.hip).
 namespace {
 static_assert(HG_NPAR == SEPVAD_HEAD_NPAR, "hpar and gpar layout (include/sepvad.h)");
-struct HeadLayout { int64_t part_stat, stat, z, dz, part_red, ub, mom, part_alpha, part_bias, part_w, total; };
-const char* head_layout(int32_t B, int32_t T, HeadLayout& L) {
+const char* head_shape(int32_t B, int32_t T) {
   if (B < 1 || B > 32767) return "need 1 <= B <= 32767";
-  if (T < 2 || T > (1 << 20)) return "need 2 <= T <= 2^20";
-  int64_t at = 0;
-  auto take = [&](int64_t bytes) { const int64_t o = at; at += (bytes + 255) / 256 * 256; return o; };
-  const int64_t n = (int64_t)CH * T;
-  L.part_stat = take((int64_t)B * hg_chunks(n, HG_STAT_E) * 2 * 8); L.stat = take((int64_t)B * 2 * 8);
-  L.z = take(B * n * 4); L.dz = take(B * n * 8);
-  L.part_red = take((int64_t)B * hg_chunks(T, HG_RED_T) * CH * 2 * 8); L.ub = take((int64_t)B * CH * 2 * 8);
-  L.mom = take((int64_t)B * 2 * 8); L.part_alpha = take((int64_t)B * hg_chunks(n, HG_DY_E) * 8);
-  L.part_bias = take((int64_t)B * MOUT * 8); L.part_w = take((int64_t)B * hg_chunks(T, HG_W_T) * HG_NW * 8);
-  L.total = at;
-  return nullptr;
+  return T < 2 || T > (1 << 20) ? "need 2 <= T <= 2^20" : nullptr;
 }
-int32_t head_check(const std::string& e, const float* y, int32_t B, int32_t T, const double* hpar, const void* scratch,
-                   int64_t scratch_bytes, HeadLayout& L, HeadArgs& a) {
-  if (const char* why = head_layout(B, T, L)) return fail(SEPVAD_E_ARG, e + why);
+// The refusals both directions share, then a's shapes, inputs and scratch arrays (sepvad_internal.h head_scratch)
+int32_t head_check(const std::string& e, const float* y, int32_t B, int32_t T, const double* hpar, void* scratch,
+                   int64_t scratch_bytes, HeadArgs& a) {
+  if (const char* why = head_shape(B, T)) return fail(SEPVAD_E_ARG, e + why);
   if (!y || !hpar) return fail(SEPVAD_E_ARG, e + "null pointer");
-  if (!scratch || scratch_bytes < L.total) return fail(SEPVAD_E_ARG, e + "scratch too small (sepvad_head_scratch_bytes)");
-  if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail(SEPVAD_E_ARG, e + "scratch must be 256-byte aligned");
-  char* sc = (char*)scratch;
   a.B = B; a.T = T; a.y = y; a.hp = hpar;
-  a.part_stat = (double*)(sc + L.part_stat); a.stat = (double*)(sc + L.stat);
-  a.z = (float*)(sc + L.z); a.dz = (double*)(sc + L.dz); a.part_red = (double*)(sc + L.part_red);
-  a.ub = (double*)(sc + L.ub); a.mom = (double*)(sc + L.mom); a.part_alpha = (double*)(sc + L.part_alpha);
-  a.part_bias = (double*)(sc + L.part_bias); a.part_w = (double*)(sc + L.part_w);
-  return SEPVAD_OK;
+  return scratch_bind(e, scratch, scratch_bytes, 256, "sepvad_head_scratch_bytes", [&](ScratchPlan& p) { head_scratch(a, p); });
 }
 }  // namespace
 
 int64_t sepvad_head_scratch_bytes(int32_t B, int32_t T) {
-  HeadLayout L{};
-  if (const char* why = head_layout(B, T, L)) return fail(SEPVAD_E_ARG, std::string("sepvad_head_scratch_bytes: ") + why);
-  return L.total;
+  if (const char* why = head_shape(B, T)) return fail(SEPVAD_E_ARG, std::string("sepvad_head_scratch_bytes: ") + why);
+  HeadArgs a{};
+  a.B = B; a.T = T;
+  return plan_bytes([&](ScratchPlan& p) { head_scratch(a, p); });
 }
 
 int32_t sepvad_head_forward(const float* y, int32_t B, int32_t T, const double* hpar, void* scratch,
                             int64_t scratch_bytes, float* masks_b, void* stream) {
-  HeadLayout L{};
   HeadArgs a{};
-  if (const int32_t rc = head_check("sepvad_head_forward: ", y, B, T, hpar, scratch, scratch_bytes, L, a)) return rc;
+  if (const int32_t rc = head_check("sepvad_head_forward: ", y, B, T, hpar, scratch, scratch_bytes, a)) return rc;
   if (!masks_b) return fail(SEPVAD_E_ARG, "sepvad_head_forward: null pointer");
   a.masks = masks_b;
   HIPRET(launch_head_forward(a, (hipStream_t)stream));
@@ -825,9 +792,8 @@ int32_t sepvad_head_forward(const float* y, int32_t B, int32_t T, const double* 
 int32_t sepvad_head_backward(const float* y, const float* G, int64_t g_b, int64_t g_m, int64_t g_t, int32_t B, int32_t T,
                              const double* hpar, void* scratch, int64_t scratch_bytes, float* g_y, double* gpar,
                              void* stream) {
-  HeadLayout L{};
   HeadArgs a{};
-  if (const int32_t rc = head_check("sepvad_head_backward: ", y, B, T, hpar, scratch, scratch_bytes, L, a)) return rc;
+  if (const int32_t rc = head_check("sepvad_head_backward: ", y, B, T, hpar, scratch, scratch_bytes, a)) return rc;
   if (!G) return fail(SEPVAD_E_ARG, "sepvad_head_backward: null pointer");
   if (g_b < 0 || g_m < 0 || g_t < 0) return fail(SEPVAD_E_ARG, "sepvad_head_backward: negative stride");
   if (!g_y && !gpar) return fail(SEPVAD_E_ARG, "sepvad_head_backward: nothing to compute");

@@ -18,22 +18,15 @@ int ws_reserve(StreamCtx* c, int B, int N) {
   if (B <= w.Bmax && Tp <= w.Tpmax) return SEPVAD_OK;
   const int Bm = std::max(B, w.Bmax), Tm = std::max(Tp, w.Tpmax);
   if (w.base) { (void)hipFree(w.base); w.base = nullptr; w.Bmax = w.Tpmax = 0; }
-  // two passes over the layout (handle.h ws_each): the size, then the pointers
+  // two passes over the layout (handle.h ws_each, ws_plan): the size, then the pointers
+  const size_t bytes = ws_bytes(Bm, Tm);
   char* base = nullptr;
-  size_t off = 0;
-  auto place = [&](auto*& p, const WsDim& d) {
-    if (base) p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
-    if (!d.overlay) off += (d.elems(Bm, Tm) * sizeof(*p) + d.slack + 255) / 256 * 256;
-  };
-  ws_each(w, place);
-  const size_t bytes = off;
   HIPCHK(hipMalloc(&base, bytes));
   // zeroed on the context's own stream, ahead of the forward that reserved it: a null-stream hipMemset is not
   // ordered with a non-blocking caller stream, and once zeroed the workspace of a concurrent forward's first launch
   // mid-run (tests/test_gpu_boundary.py::test_two_streams_concurrently_match_serial, round 4)
   HIPCHK(hipMemsetAsync(base, 0, bytes, (hipStream_t)c->stream));
-  off = 0;
-  ws_each(w, place);
+  ws_plan(w, base, Bm, Tm);
   w.base = base; w.bytes = bytes; w.Bmax = Bm; w.Tpmax = Tm;
   return SEPVAD_OK;
 }

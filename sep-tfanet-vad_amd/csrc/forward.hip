@@ -566,6 +566,19 @@ int enqueue_chunk(sepvad_model* h, StreamCtx* cx, const float* x, int ldx, int b
 }
 }  // namespace
 
+int tail_stages(sepvad_model* h, const Workspace& w, const float* x, int ldx, int B, int N, float* sep, float* vad,
+                hipStream_t s) {
+  const int T = 1 + N / HOP;
+  Knobs kn{}; kn.vad_feat = KNOB_UNSET;  // not read_knobs(): no probe may write the handle here
+  const SepVadOutputs out{sep, vad};
+  const Chunk k{h, nullptr, w, 0, B, N, T, round_up(T, TILE), &out, s, nullptr, kn};
+  const bool has_vad = h->cfg.final_vad != 0;  // (its masked-speakers variant is refused by the caller)
+  bool taps_in_istft = false;
+  if (const int rc = k.front_end(x, ldx, 0, 0)) return rc;
+  if (const int rc = k.vad_stage(has_vad, false, &taps_in_istft)) return rc;
+  return k.back_end(nullptr, has_vad, false, taps_in_istft, 0, 0);
+}
+
 int forward_impl(sepvad_model* h, const float* x, int ldx, int B, int N, const SepVadOutputs* out,
                  const SepVadInferKw* kw, hipStream_t s, int nstr, long long hopw) {
   const int T = 1 + N / HOP;

@@ -10,6 +10,7 @@
 
 #include "../../include/sepvad.h"
 #include "pack.h"
+#include "scratch_plan.h"
 
 namespace sepvad {
 // The calling thread's sepvad_last_error text (api.hip); fail returns `code`.
@@ -41,6 +42,10 @@ struct Workspace {
 // one utterance (1: per frame; 0: per utterance; a record producer's rows per workgroup), `slack` bytes after the
 // array. Every array is utterance-major and starts on a 256-byte boundary. D32 overlays the Dhi and Dlo planes.
 struct WsDim {
+  // slack: the record arrays carry the 16 bytes their first hand-written layout gave them. Nothing reads or writes
+  // them: a producer (k_stft_gate, k_vad1, the statistics kernels) stores exactly its own record through
+  // block_reduce_store, and reduce_records and its staged variants (k_tcn, the res_out GEMM) load records r < n
+  // only, value by value. A caller-owned copy of such an array (the tail's scratch) needs none.
   int n, rows = 1, slack = 0;
   bool overlay = false;  // shares the bytes of the arrays that follow
   size_t elems(int B, int Tp) const { return (size_t)B * (rows ? Tp / rows : 1) * n; }
@@ -66,6 +71,15 @@ inline Workspace ws_view(const Workspace& w, int b0, int Tp) {
   ws_each(v, [&](auto*& p, const WsDim& d) { p += d.elems(b0, Tp); });
   return v;
 }
+
+// One pass of the planner over the layout: the arrays of w at `base` (null: none is written) for B utterances of Tp
+// frames; returns the bytes. ws_bytes: the size pass alone, a pure host function.
+inline size_t ws_plan(Workspace& w, char* base, int B, int Tp) {
+  ScratchPlan p(base);
+  ws_each(w, [&](auto*& a, const WsDim& d) { d.overlay ? p.overlay(a) : p.take(a, d.elems(B, Tp), d.slack); });
+  return p.bytes();
+}
+inline size_t ws_bytes(int B, int Tp) { Workspace w{}; return ws_plan(w, nullptr, B, Tp); }
 
 constexpr int MAX_SPLIT = 4;
 constexpr int TCLK_RECS = 4096;  // SEPVAD_TCN_CLOCK records kept (ring)
@@ -189,6 +203,11 @@ int check_giveup(StreamCtx* c, const Knobs& kn);
 // Utterance u of a forward reads x + (u % nstr) * ldx + (u / nstr) * hopw (nstr = 0: a plain batch, row u at u * ldx)
 int forward_impl(sepvad_model* h, const float* x, int ldx, int B, int N, const SepVadOutputs* out,
                  const SepVadInferKw* kw, hipStream_t s, int nstr = 0, long long hopw = 0);
+// The forward's own front end, multi-kernel VAD stage and back end on the caller's workspace (X, specdb, S0, rec_gate,
+// vy, rec_vad and its frame-major masks) for sepvad_tail_forward: no keywords, knobs, probes or timing, outputs sep and
+// vad only. Touches nothing mutable of the handle (no h->mu needed).
+int tail_stages(sepvad_model* h, const Workspace& w, const float* x, int ldx, int B, int N, float* sep, float* vad,
+                hipStream_t s);
 // sepvad_side_outputs with h->mu held by the caller (so a check of the forward's identity and the copies it guards
 // are one critical section: no forward can be enqueued on the stream in between)
 int side_outputs_locked(sepvad_model* h, const SepVadOutputs* out, void* stream);

@@ -11,6 +11,8 @@
 #include <hip/hip_fp16.h>
 #include <cstdint>
 
+#include "scratch_plan.h"
+
 namespace sepvad {
 
 constexpr int NFFT = 512;   // n_fftBins (model/model.py:362)
@@ -321,11 +323,9 @@ struct StoiArgs {
   double* ex_part; int ex_nchunk;   // [R][ex_nchunk] chunk partials of the extended correlation (scratch)
 };
 constexpr int STOI_MODE_CLASSIC = 1, STOI_MODE_EXTENDED = 2;  // SEPVAD_STOI_CLASSIC / _EXTENDED (api.hip asserts)
-long long stoi_scratch_layout(int R, long long N, int up, int down, StoiArgs* a, char* base);  // bytes
-long long stoi_ex_scratch_layout(int R, long long N, int up, int down, int modes, StoiArgs* a, char* base);
+void stoi_scratch(StoiArgs& a, int modes, ScratchPlan& p);  // the scratch arrays of a call with `modes`, each once
 hipError_t launch_stoi_ex(const StoiArgs& a, int modes, hipStream_t s);
 hipError_t stoi_tables(int fs_sig, StoiArgs& a);  // device-resident taps / window / twiddles of the current device
-hipError_t launch_stoi(const StoiArgs& a, hipStream_t s);
 constexpr int VACC_MAX_S = 8;
 struct VadAccArgs {
   float* preds; const float* targets;   // [B][S][T]
@@ -455,6 +455,13 @@ struct HeadArgs {
   float* g_y;                         // [B][256][T] (null: parameter gradients only)
   double* gpar;                       // [HG_NPAR] (null: the input gradient only)
 };
+// The scratch, each array once (a.B and a.T are set): the statistics and z of both directions, then the backward's
+inline void head_scratch(HeadArgs& a, ScratchPlan& p) {
+  const size_t B = a.B, n = (size_t)CH * a.T;
+  p.take(a.part_stat, B * hg_chunks(n, HG_STAT_E) * 2); p.take(a.stat, B * 2); p.take(a.z, B * n); p.take(a.dz, B * n);
+  p.take(a.part_red, B * hg_chunks(a.T, HG_RED_T) * CH * 2); p.take(a.ub, B * CH * 2); p.take(a.mom, B * 2);
+  p.take(a.part_alpha, B * hg_chunks(n, HG_DY_E)); p.take(a.part_bias, B * MOUT); p.take(a.part_w, B * hg_chunks(a.T, HG_W_T) * HG_NW);
+}
 hipError_t launch_head_forward(const HeadArgs& a, hipStream_t s);
 hipError_t launch_head_backward(const HeadArgs& a, hipStream_t s);
 

@@ -384,44 +384,21 @@ __global__ __launch_bounds__(ST_THREADS) void k_stoi_ex_finish(StoiArgs a) {
   if (t == 0) a.out_ex[r] = sum / ((double)J * STOI_SEG);
 }
 
-static size_t st_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-long long stoi_scratch_layout(int R, long long N, int up, int down, StoiArgs* a, char* base) {
-  const long long L = stoi_resampled_len(N, up, down);
-  const long long nF = stoi_num_frames(L);
-  const long long Ls = (L + 3) & ~3LL;
-  size_t off = 0;
-  const size_t o_sig = off;    off = st_align(off + (up == down ? 0 : (size_t)R * 2 * Ls * sizeof(float)));
-  const size_t o_energy = off; off = st_align(off + (size_t)R * nF * sizeof(double));
-  const size_t o_kept = off;   off = st_align(off + (size_t)R * nF * sizeof(int));
-  const size_t o_nkept = off;  off = st_align(off + (size_t)R * sizeof(int));
-  const size_t o_tob = off;    off = st_align(off + (size_t)R * 2 * STOI_BANDS * nF * sizeof(double));
-  if (a) {
-    a->L = L; a->nF = (int)nF; a->Ls = Ls;
-    a->sig = reinterpret_cast<float*>(base + o_sig);
-    a->energy = reinterpret_cast<double*>(base + o_energy);
-    a->kept = reinterpret_cast<int*>(base + o_kept);
-    a->nkept = reinterpret_cast<int*>(base + o_nkept);
-    a->tob = reinterpret_cast<double*>(base + o_tob);
-  }
-  return (long long)off;
-}
-
-// The classic layout, then (modes & STOI_MODE_EXTENDED) the chunk partials [R][ex_nchunk] of k_stoi_ex_corr, sized
-// for every frame kept like the rest.
-long long stoi_ex_scratch_layout(int R, long long N, int up, int down, int modes, StoiArgs* a, char* base) {
-  size_t off = (size_t)stoi_scratch_layout(R, N, up, down, a, base);
-  if (modes & STOI_MODE_EXTENDED) {
-    const long long nF = stoi_num_frames(stoi_resampled_len(N, up, down));
+// The scratch of one call, each array once, sized for every frame kept (a.N, a.R, a.up and a.down are set; fills L, Ls,
+// nF and ex_nchunk). sig is empty for the identity resampler: it then shares energy's address and takes no bytes.
+void stoi_scratch(StoiArgs& a, int modes, ScratchPlan& p) {
+  a.L = stoi_resampled_len(a.N, a.up, a.down);
+  a.Ls = (a.L + 3) & ~3LL;
+  const long long nF = stoi_num_frames(a.L);
+  a.nF = (int)nF;
+  const size_t R = a.R;
+  p.take(a.sig, a.up == a.down ? 0 : R * 2 * a.Ls);
+  p.take(a.energy, R * nF); p.take(a.kept, R * nF); p.take(a.nkept, R); p.take(a.tob, R * 2 * STOI_BANDS * nF);
+  if (modes & STOI_MODE_EXTENDED) {  // the chunk partials of k_stoi_ex_corr
     const long long J = std::max(1LL, nF - 1 - (STOI_SEG - 1));
-    const long long nc = (J + ST_EX_CHUNK - 1) / ST_EX_CHUNK;
-    if (a) {
-      a->ex_nchunk = (int)nc;
-      a->ex_part = reinterpret_cast<double*>(base + off);
-    }
-    off = st_align(off + (size_t)R * nc * sizeof(double));
+    a.ex_nchunk = (int)((J + ST_EX_CHUNK - 1) / ST_EX_CHUNK);
+    p.take(a.ex_part, R * a.ex_nchunk);
   }
-  return (long long)off;
 }
 
 // Device copies of the host design, one per (device, rate), made on first use and kept for the life of the process.
@@ -488,13 +465,7 @@ static hipError_t launch_stoi_classic(const StoiArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_stoi(const StoiArgs& a, hipStream_t s) {
-  const hipError_t e = launch_stoi_front(a, s);
-  return e != hipSuccess ? e : launch_stoi_classic(a, s);
-}
-
-// modes: STOI_MODE_CLASSIC (a.out) | STOI_MODE_EXTENDED (a.out_ex, a.ex_part); the classic result comes from the
-// launches of launch_stoi
+// modes: STOI_MODE_CLASSIC (a.out) | STOI_MODE_EXTENDED (a.out_ex, a.ex_part)
 hipError_t launch_stoi_ex(const StoiArgs& a, int modes, hipStream_t s) {
   hipError_t e = launch_stoi_front(a, s);
   if (e != hipSuccess) return e;

@@ -57,8 +57,7 @@ def eval_separation(est, tgt, mix=None, sdr_type="sisdr", zero_mean=True, take_l
         mix, mld = _native.rows2(mix)
     B, _, N = est.shape
     if scratch is None:
-        scratch = _native.scratch(dev, _native.query_bytes(lib.sepvad_eval_scratch_bytes, "sepvad_eval_scratch_bytes",
-                                                           B, N))
+        scratch, _ = _native.scratch_for("sepvad_eval_scratch_bytes", dev, B, N)
     pw = torch.empty(B, 2, 2, dtype=torch.float32, device=dev)
     min_loss = torch.empty(B, dtype=torch.float32, device=dev)
     perm = torch.empty(B, 2, dtype=torch.int64, device=dev)

@@ -97,19 +97,17 @@ class LiveSeparator:
         self.Rt = max(self.win - self.hop, self.hop)  # stitched tail: the PIT reads at most win - hop samples
         cfg = self._h.cfg
         self.T = 1 + self.win // (cfg["n_fftBins"] // 2)
-        has_vad = bool(cfg["final_vad"]) and (not cfg["final_vad_masked_speakers"] or cfg["noisy_phase"])
         # window k contributes the frames centred on the multiples of 256 inside its emitted hop: its last hop / 256
         # frames when the hop is a multiple of 256 and the window is not (frame T - 1 = floor(win / 256) is then
         # centred before the window's end; a window of a whole number of frames has that frame centred ON its end,
         # in the next hop, and gets no VAD track)
         tiles = self.hop % VAD_HOP == 0 and self.win % VAD_HOP != 0
-        self.vad_frames = self.hop // VAD_HOP if has_vad and tiles else 0
+        self.vad_frames = self.hop // VAD_HOP if self._h.has_vad and tiles else 0
         self._ring = torch.empty(B, 2 * self.R, dtype=torch.float32, device=self.device)
         self._tail = torch.empty(B, 2, 2 * self.Rt, dtype=torch.float32, device=self.device)
         nbytes = 0
         if self.per_stream:
-            nbytes = _native.query_bytes(self._lib.sepvad_pit_l1_rows_scratch_bytes, "sepvad_pit_l1_rows_scratch_bytes",
-                                         B, self.win - self.hop)
+            nbytes = _native.scratch_bytes("sepvad_pit_l1_rows_scratch_bytes", B, self.win - self.hop)
         self._scratch = torch.empty(max(nbytes, _pit.PIT_SCRATCH_BYTES) // 8, dtype=torch.float64, device=self.device)
         self._h.reserve(B * self.max_pending, self.win)
         self.reset()

@@ -159,8 +159,7 @@ def stoi_pairs(X, Y, fs_sig, xidx=None, yidx=None):
     N = X.shape[1]
     R = len(xidx) if xidx is not None else X.shape[0]
     dev = X.device
-    scratch = _native.scratch(dev, _native.query_bytes(lib.sepvad_stoi_scratch_bytes, "sepvad_stoi_scratch_bytes",
-                                                       R, N, int(fs_sig)))
+    scratch, _ = _native.scratch_for("sepvad_stoi_scratch_bytes", dev, R, N, int(fs_sig))
     out = torch.empty(R, device=dev, dtype=torch.float64)
     frames = torch.empty(R, device=dev, dtype=torch.int32)
     xi = torch.as_tensor(xidx, dtype=torch.int32, device=dev) if xidx is not None else None
@@ -184,8 +183,7 @@ def _stoi_ex(X, Y, fs_sig, xidx, yidx, modes):
     N = X.shape[1]
     R = len(xidx) if xidx is not None else X.shape[0]
     dev = X.device
-    scratch = _native.scratch(dev, _native.query_bytes(lib.sepvad_stoi_ex_scratch_bytes,
-                                                       "sepvad_stoi_ex_scratch_bytes", R, N, int(fs_sig), modes))
+    scratch, _ = _native.scratch_for("sepvad_stoi_ex_scratch_bytes", dev, R, N, int(fs_sig), modes)
     d = torch.empty(R, device=dev, dtype=torch.float64) if modes & STOI_CLASSIC else None
     e = torch.empty(R, device=dev, dtype=torch.float64) if modes & STOI_EXTENDED else None
     frames = torch.empty(R, device=dev, dtype=torch.int32)

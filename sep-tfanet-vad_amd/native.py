@@ -208,12 +208,26 @@ def scratch(device, nbytes):
     return buf
 
 
-def query_bytes(fn, what, *args):
-    """A host size query (sepvad_*_scratch_bytes): its answer, or the error of its negative status."""
-    nbytes = fn(*args)
+def scratch_bytes(query, *args):
+    """The answer of the host size query `query` (a sepvad_*_scratch_bytes name of _ABI), or the error of its status."""
+    nbytes = getattr(load_library(), query)(*args)
     if nbytes < 0:
-        check(nbytes, what)
+        check(nbytes, query)
     return nbytes
+
+
+def scratch_for(query, device, *args):
+    """(the current stream's scratch on `device`, nbytes) for an entry whose size query `query` answers nbytes."""
+    nbytes = scratch_bytes(query, *args)
+    return scratch(device, nbytes), nbytes
+
+
+def frame_major_masks(masks_b, device=None):
+    """Pre-sigmoid masks [B, 514, T] or [B, 2, 257, T] as the forward keeps them: frame-major, zero-padded [B, Tp, 576]"""
+    B, T = masks_b.shape[0], masks_b.shape[-1]
+    mf = torch.zeros(B, (T + 63) // 64 * 64, 576, device=device or masks_b.device, dtype=torch.float32)
+    mf[:, :T, :514] = masks_b.to(mf.device, torch.float32).reshape(B, 514, T).transpose(1, 2)
+    return mf
 
 
 def rows3(t):
@@ -365,6 +379,11 @@ class Handle:
     def _stream(self):
         return stream_ptr(self.device)
 
+    @property
+    def has_vad(self):
+        """Whether the forward produces a VAD track (model/model.py:424-427)."""
+        return bool(self.cfg["final_vad"]) and (not self.cfg["final_vad_masked_speakers"] or self.cfg["noisy_phase"])
+
     def forward(self, x: torch.Tensor, inference_kw=None, return_aux: bool = False, outputs: dict | None = None):
         """One forward. Returns dict(sep, vad, est[, spectrum, masks_b, mask_per_speaker])."""
         if x.device.type != "cuda":
@@ -380,9 +399,8 @@ class Handle:
         dev = self.device
         o = outputs or {}
         sep = o.get("sep") if o.get("sep") is not None else torch.empty(B, S, N, device=dev, dtype=torch.float32)
-        has_vad = bool(self.cfg["final_vad"]) and (not self.cfg["final_vad_masked_speakers"] or self.cfg["noisy_phase"])
         vad = (o.get("vad") if o.get("vad") is not None else torch.empty(B, S, T, device=dev, dtype=torch.float32)) \
-            if has_vad else None
+            if self.has_vad else None
         est = o.get("est") if o.get("est") is not None else torch.empty(B, S, F, T, device=dev, dtype=torch.complex64)
         spectrum = masks_b = mask = None
         if return_aux:
@@ -425,8 +443,7 @@ class Handle:
         S = self.cfg["num_spk"]
         T = 1 + N // (self.cfg["n_fftBins"] // 2)
         sep = torch.empty(n_win, B, S, N, device=self.device, dtype=torch.float32)
-        has_vad = bool(self.cfg["final_vad"]) and (not self.cfg["final_vad_masked_speakers"] or self.cfg["noisy_phase"])
-        vad = torch.empty(n_win * B, S, T, device=self.device, dtype=torch.float32) if has_vad else None
+        vad = torch.empty(n_win * B, S, T, device=self.device, dtype=torch.float32) if self.has_vad else None
         outs = SepVadOutputs(_ptr(sep).value, _ptr(vad).value, 0, 0, 0, 0)
         kw = make_kw(inference_kw)
         ld = x.stride(0) if B > 1 else x.shape[1]
@@ -532,8 +549,7 @@ class Handle:
         Tp = (T + 63) // 64 * 64
         Xf = torch.zeros(B, Tp, 257, device=self.device, dtype=torch.complex64)
         Xf[:, :T] = X.to(self.device, torch.complex64).transpose(1, 2)
-        mf = torch.zeros(B, Tp, 576, device=self.device, dtype=torch.float32)
-        mf[:, :T, :514] = masks.to(self.device, torch.float32).reshape(B, 514, T).transpose(1, 2)
+        mf = frame_major_masks(masks, self.device)
         y = torch.empty(B, 2, N, device=self.device, dtype=torch.float32)
         est = torch.empty(B, 2, 257, T, device=self.device, dtype=torch.complex64)
         _check(self._lib.sepvad_istft_pair_test(self._h, _ptr(Xf), _ptr(mf), B, N, _ptr(y), _ptr(est), self._stream()),

@@ -91,8 +91,7 @@ class StreamEval:
         if tuple(sep_w.shape[1:]) != (self.B, 2, self.W) or sep_w.dtype != torch.float32 or not sep_w.is_contiguous():
             raise ValueError(f"StreamEval.push: expected contiguous float32 [n, {self.B}, 2, {self.W}], got "
                              f"{tuple(sep_w.shape)}")
-        nbytes = _native.query_bytes(self.lib.sepvad_stream_eval_scratch_bytes, "sepvad_stream_eval_scratch_bytes",
-                                     self.B, n, self.W, self.H, self.mode)
+        nbytes = _native.scratch_bytes("sepvad_stream_eval_scratch_bytes", self.B, n, self.W, self.H, self.mode)
         if self.scratch is None or self.scratch.numel() * 8 < nbytes:
             self.scratch = torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.float64, device=sep_w.device)
         P = _native.ptr

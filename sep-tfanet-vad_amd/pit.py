@@ -57,8 +57,7 @@ def pit_l1_rows(est: torch.Tensor, ref: torch.Tensor):
     ref, rld = _native.rows3(ref)
     B, _, L = est.shape
     dev = est.device
-    nbytes = _native.query_bytes(lib.sepvad_pit_l1_rows_scratch_bytes, "sepvad_pit_l1_rows_scratch_bytes", B, L)
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    scratch, nbytes = _native.scratch_for("sepvad_pit_l1_rows_scratch_bytes", dev, B, L)
     perm = torch.empty(B, 2, dtype=torch.int64, device=dev)
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     pw = torch.empty(B, 2, 2, dtype=torch.float32, device=dev)

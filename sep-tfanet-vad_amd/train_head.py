@@ -33,11 +33,6 @@ HEAD_PARAMS = ("TCN.output.0.weight", "TCN.output.1.weight", "TCN.output.1.bias"
                "TCN.output.2.weight_v", "TCN.output.2.bias")
 
 
-def _scratch(lib, dev, B, T):
-    nbytes = _native.query_bytes(lib.sepvad_head_scratch_bytes, "sepvad_head_scratch_bytes", B, T)
-    return _native.scratch(dev, nbytes), nbytes
-
-
 def _head_weights(params):
     """The six parameters as hpar: float64, the weight folded, in gpar's layout."""
     alpha, gam, bet, wg, wv, bias = params
@@ -55,7 +50,7 @@ class _Head(torch.autograd.Function):
         y32 = y.detach().to(torch.float32).contiguous()
         masks = torch.empty(B, MOUT, T, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            buf, nbytes = _scratch(lib, dev, B, T)
+            buf, nbytes = _native.scratch_for("sepvad_head_scratch_bytes", dev, B, T)
             hpar = _head_weights(params)
             _native.check(lib.sepvad_head_forward(_native.ptr(y32), B, T, _native.ptr(hpar), _native.ptr(buf), nbytes,
                                                   _native.ptr(masks), _native.stream_ptr(dev)), "sepvad_head_forward")
@@ -79,7 +74,7 @@ class _Head(torch.autograd.Function):
         g_y = torch.empty(B, CH, T, device=dev, dtype=torch.float32) if want_y else None
         gpar = torch.empty(HEAD_NPAR, device=dev, dtype=torch.float64) if want_p else None
         with torch.cuda.device(dev):
-            buf, nbytes = _scratch(lib, dev, B, T)
+            buf, nbytes = _native.scratch_for("sepvad_head_scratch_bytes", dev, B, T)
             hpar = _head_weights(params)
             rc = lib.sepvad_head_backward(_native.ptr(y32), _native.ptr(g), *g.stride(), B, T, _native.ptr(hpar),
                                           _native.ptr(buf), nbytes, _native.ptr(g_y), _native.ptr(gpar),

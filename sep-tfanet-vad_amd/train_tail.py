@@ -33,11 +33,6 @@ VAD_PARAMS = ("common.conv1_1.weight_g", "common.conv1_1.weight_v", "common.conv
               "output_layer_vad.bias")
 
 
-def _scratch(lib, dev, B, N):
-    nbytes = _native.query_bytes(lib.sepvad_tail_scratch_bytes, "sepvad_tail_scratch_bytes", B, N)
-    return _native.scratch(dev, nbytes), nbytes
-
-
 def _fold(v, g):
     """w = v g / |v| in float64 (torch weight_norm, dim 0)."""
     v64 = v.detach().double()
@@ -74,12 +69,10 @@ class _Tail(torch.autograd.Function):
         if state.get("outputs") is not None:  # tail(x): the native forward's own tensors
             sep, vad = state["outputs"]
         else:
-            Tp = (T + 63) // 64 * 64
-            mf = torch.zeros(B, Tp, 576, device=dev, dtype=torch.float32)
-            mf[:, :T, :2 * NBIN] = m32.transpose(1, 2)
+            mf = _native.frame_major_masks(m32)
             sep = torch.empty(B, 2, N, device=dev, dtype=torch.float32)
             vad = torch.empty(B, 2, T, device=dev, dtype=torch.float32) if has_vad else None
-            buf, nbytes = _scratch(lib, dev, B, N)
+            buf, nbytes = _native.scratch_for("sepvad_tail_scratch_bytes", dev, B, N)
             _native.check(lib.sepvad_tail_forward(h.raw, _native.ptr(x), state["ldx"], _native.ptr(mf), B, N,
                                                   _native.ptr(buf), nbytes, _native.ptr(sep), _native.ptr(vad),
                                                   _native.stream_ptr(dev)), "sepvad_tail_forward")
@@ -108,7 +101,7 @@ class _Tail(torch.autograd.Function):
         _native.require_device("train_tail backward", x, g_sep, g_vad)
         g_masks = torch.empty(B, 2 * NBIN, T, device=dev, dtype=torch.float32) if want_m else None
         gpar = torch.empty(_NW1 + 26, device=dev, dtype=torch.float64) if want_p else None
-        buf, nbytes = _scratch(lib, dev, B, N)
+        buf, nbytes = _native.scratch_for("sepvad_tail_scratch_bytes", dev, B, N)
         vadw = _vad_weights(params) if g_vad is not None else None
         ss = g_sep.stride() if g_sep is not None else (0, 0, 0)
         sv = g_vad.stride() if g_vad is not None else (0, 0, 0)

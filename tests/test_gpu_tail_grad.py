@@ -274,6 +274,26 @@ def test_refusals(net, tail, state_dicts):
         gm.sum().backward()
 
 
+def test_scratch_refusals(net):
+    """Both entries refuse a scratch one byte too small, a null one and one 8 bytes off its alignment, in these words
+    and before anything is launched (tests/test_scratch_host.py has the entries that need no handle)."""
+    import ctypes
+    from sep_tfanet_vad_amd import native
+    lib, h = native.load_library(), net.native_handle(DEV)
+    B, N = 1, 2816
+    need = lib.sepvad_tail_scratch_bytes(B, N)
+    one, off8 = ctypes.c_void_p(4096), ctypes.c_void_p(4096 + 8)  # never dereferenced
+    calls = {
+        "sepvad_tail_forward": lambda s, n: lib.sepvad_tail_forward(h.raw, one, N, one, B, N, s, n, one, one, None),
+        "sepvad_tail_backward": lambda s, n: lib.sepvad_tail_backward(h.raw, one, N, one, B, N, one, 0, 0, 0, one, 0, 0, 0,
+                                                                      one, s, n, one, one, None)}
+    for entry, call in calls.items():
+        for s, n, text in ((one, need - 1, "scratch too small (sepvad_tail_scratch_bytes)"),
+                           (None, need, "scratch too small (sepvad_tail_scratch_bytes)"),
+                           (off8, need, "scratch must be 256-byte aligned")):
+            assert call(s, n) == -1 and lib.sepvad_last_error().decode() == f"{entry}: {text}"
+
+
 # ---- 6. bits ---------------------------------------------------------------------------------------------------------
 
 def run_bits(tail, x, masks, grads):

@@ -102,8 +102,7 @@ def main():
             r = gc.restated_criterion(sep, tgt, vad, labels)
             (0.99 * r["sep"] + 0.01 * r["vad"]).backward()
 
-        nbytes = native.query_bytes(lib.sepvad_head_scratch_bytes, "sepvad_head_scratch_bytes", B, T)
-        buf = native.scratch(dev, nbytes)
+        buf, nbytes = native.scratch_for("sepvad_head_scratch_bytes", dev, B, T)
         hpar = train_head._head_weights(head._params())
         masks = torch.empty(B, 514, T, device=dev)
         g_y = torch.empty(B, 256, T, device=dev)

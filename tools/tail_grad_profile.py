@@ -85,8 +85,7 @@ def main():
             sep, vad = tc.restated_tail(x, masks, params, win, win)
             torch.autograd.backward([sep, vad], [g_sep, g_vad])
 
-        nbytes = native.query_bytes(lib.sepvad_tail_scratch_bytes, "sepvad_tail_scratch_bytes", B, N)
-        buf = native.scratch(dev, nbytes)
+        buf, nbytes = native.scratch_for("sepvad_tail_scratch_bytes", dev, B, N)
         g_masks = torch.empty(B, 514, T, device=dev)
         gpar = torch.empty(5166, device=dev, dtype=torch.float64)
         vadw = train_tail._vad_weights(tail._params())
